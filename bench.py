@@ -27,11 +27,22 @@ touches the GPU) and exits with its status; every rank asserts world_size == --g
 --dist-backend gloo the exchange runs through host copies and ranks may share a GPU (rank r on
 cuda:(r mod device_count)) -- the -m gpu test runs 2 ranks on one MI355X that way.
 
-Correctness gate before timing: every round verifies, then a negative control -- one signature per
-rank corrupted (bit flip in x) must make exactly that round and the next one reject, with first_bad
-= the lowest corrupted round over all ranks.
+A plain run does what the headline figure needs and no more: generate the history, --warmup steps,
+--steps timed steps, one JSON line (the per-stage and roofline figures in it come from events
+recorded inside the timed steps, not from runs of their own).
 
-Usage: python bench.py [--gpus N --steps K --warmup W --n BEACONS_PER_GPU]
+--full adds the checks and side measurements. Correctness gate before timing: every round verifies,
+then a negative control -- one signature per rank corrupted (bit flip in x) must make exactly that
+round and the next one reject, with first_bad = the lowest corrupted round over all ranks. After
+timing, at N=1: the cpu_baseline leg (the C oracle over a sample of the same history).
+
+--dump-outputs DIR writes what the last timed step returned to its caller, as rank 0 holds it:
+DIR/ok.npy (float32, one 0/1 verdict per round, in round order; above DUMP_MAX_ROUNDS rounds a
+sorted sample of that many positions drawn with the fixed seed DUMP_SEED) and DIR/first_bad.npy
+(float64, the first rejected round, -1 when every round verified). The history is a pure function
+of the arguments (fixed key, fixed generator seeds), so two builds can be compared file for file.
+
+Usage: python bench.py [--gpus N --steps K --warmup W --n BEACONS_PER_GPU] [--full] [--dump-outputs DIR]
        python bench.py --gpus 8 --total-rounds 100000000          (configs[3], 8 ranks over RCCL)
        python bench.py --total-rounds 100000000 --slice 7/8      (one shard of it in one process)
        (or launched per rank: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N)
@@ -51,6 +62,8 @@ sys.path.insert(0, ROOT)
 
 LIMB_PRODUCTS_PER_FP_MUL = 288  # algorithmic unit: 12x32-bit Montgomery = 144 (a*b) + 144 (m*p) limb products
 PMC_FILE = "r06z_pmc_traffic.json"
+DUMP_MAX_ROUNDS = 8_000_000  # --dump-outputs: 32 MB of float32 verdicts at the most
+DUMP_SEED = 0xD7A4D
 
 
 def load_json(rel):
@@ -109,6 +122,27 @@ def cpu_baseline(pk48, segments, workers):
         oks = list(ex.map(run, jobs))
         dt = time.perf_counter() - t0
     return n / dt, sum(oks), n
+
+
+def unpack_verdicts(words, total):
+    """The verdict bitmap (int64 words, bit i % 64 of word i // 64 = round i accepted) as one bool per
+    round, the `total` rounds it covers."""
+    import numpy as np
+
+    return np.unpackbits(np.ascontiguousarray(words).view(np.uint8), bitorder="little")[:total].astype(bool)
+
+
+def dump_outputs(path, fbv, ok):
+    """--dump-outputs: ok.npy (float32, one 0/1 verdict per round in round order; above
+    DUMP_MAX_ROUNDS rounds the verdicts at that many sorted positions drawn with DUMP_SEED) and
+    first_bad.npy (float64, the first rejected round, -1 for none) under `path`."""
+    import numpy as np
+
+    if len(ok) > DUMP_MAX_ROUNDS:
+        ok = ok[np.sort(np.random.default_rng(DUMP_SEED).integers(0, len(ok), DUMP_MAX_ROUNDS))]
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "ok.npy"), ok.astype(np.float32))
+    np.save(os.path.join(path, "first_bad.npy"), np.array([-1 if fbv is None else fbv], np.float64))
 
 
 def free_port():
@@ -188,9 +222,16 @@ def main():
     ap.add_argument("--launch-check", action="store_true",
                     help="start the ranks, form the process group, run one exchange on host tensors and print "
                          "one JSON line per rank, without touching a GPU (CPU test of the N-rank launch)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the correctness gate (all accept + negative control) before timing and, at "
+                         "one rank, the cpu_baseline leg after it; a plain run only times the steps")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the verdicts of the last timed step to DIR/ok.npy and DIR/first_bad.npy")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
 
@@ -300,44 +341,48 @@ def main():
             return shard.combine(first_bad, bitmap, n, to_host=False, counts=counts)
         return first_bad, bitmap
 
-    def verdicts():
-        fb, bm = step()
-        torch.cuda.synchronize(dev)
+    def decode(fb, bm):  # what one step returned, on the host: (first bad round or None, verdict per round)
         total = sum(counts) if use_pg else n
-        ok = np.unpackbits(bm.cpu().numpy().view(np.uint8), bitorder="little")[:total].astype(bool)
+        ok = unpack_verdicts(bm.cpu().numpy(), total)
         fbv = int(fb.item()) & (2 ** 64 - 1)
         return (None if fbv in (2 ** 64 - 1, shard.NONE_I64) else fbv), ok
+
+    def verdicts():
+        ret = step()
+        torch.cuda.synchronize(dev)
+        return decode(*ret)
 
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize(dev)
-    # correctness gate 1: every generated round verifies
-    fbv, ok = verdicts()
-    assert fbv is None and ok.all(), f"verification failed: first_bad={fbv} rejected={int((~ok).sum())}"
-    # gate 2 (negative control): one corrupted signature per rank -> exactly it and its successor reject
-    def bad_index(count, ph):  # a round whose successor is in the same segment (its prev = the bad sig)
-        b = count // 2
-        return b - 1 if b > 0 and (b + 1 + ph) % seg == 0 else b
+    if args.full:
+        # correctness gate 1: every generated round verifies
+        fbv, ok = verdicts()
+        assert fbv is None and ok.all(), f"verification failed: first_bad={fbv} rejected={int((~ok).sum())}"
+        # gate 2 (negative control): one corrupted signature per rank -> exactly it and its successor reject
+        def bad_index(count, ph):  # a round whose successor is in the same segment (its prev = the bad sig)
+            b = count // 2
+            return b - 1 if b > 0 and (b + 1 + ph) % seg == 0 else b
 
-    if strong:
-        phases = [shard.segmented_slice(args.total_rounds, s_world, r, seg).phase for r in range(s_world)]
-    else:
-        phases = [0] * world
-    bad_i = bad_index(n, phase)
-    saved = sigs[bad_i].clone()
-    sigs[bad_i, 50] ^= 1  # bit flip in x.c0
-    fbv, ok = verdicts()
-    sigs[bad_i].copy_(saved)
-    gate = list(zip(counts, phases)) if use_pg else [(n, phase)]
-    want = np.ones(len(ok), bool)
-    for r, (c, ph) in enumerate(gate):
-        off, b = sum(x[0] for x in gate[:r]), bad_index(c, ph)
-        want[off + b] = False
-        if b + 1 < c:
-            want[off + b + 1] = False
-    want_fb = (first_round - (sum(counts[:rank]) if use_pg else 0)) + bad_index(*gate[0])
-    assert (ok == want).all() and fbv == want_fb, f"negative control failed: first_bad={fbv} want {want_fb} " \
-        f"rejected={np.flatnonzero(~ok)[:8].tolist()}"
+        if strong:
+            phases = [shard.segmented_slice(args.total_rounds, s_world, r, seg).phase for r in range(s_world)]
+        else:
+            phases = [0] * world
+        bad_i = bad_index(n, phase)
+        saved = sigs[bad_i].clone()
+        sigs[bad_i, 50] ^= 1  # bit flip in x.c0
+        fbv, ok = verdicts()
+        sigs[bad_i].copy_(saved)
+        gate = list(zip(counts, phases)) if use_pg else [(n, phase)]
+        want = np.ones(len(ok), bool)
+        for r, (c, ph) in enumerate(gate):
+            off, b = sum(x[0] for x in gate[:r]), bad_index(c, ph)
+            want[off + b] = False
+            if b + 1 < c:
+                want[off + b + 1] = False
+        want_fb = (first_round - (sum(counts[:rank]) if use_pg else 0)) + bad_index(*gate[0])
+        assert (ok == want).all() and fbv == want_fb, f"negative control failed: first_bad={fbv} want {want_fb} " \
+            f"rejected={np.flatnonzero(~ok)[:8].tolist()}"
 
     eng.profile(True)
     eng.profile_read()
@@ -346,7 +391,7 @@ def main():
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     torch.cuda.synchronize(dev)
     if use_pg:
         dist.barrier()
@@ -357,6 +402,9 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=dev if args.dist_backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+
+    if args.dump_outputs and rank == 0:  # the last timed step's verdicts, as its caller received them
+        dump_outputs(args.dump_outputs, *decode(*last))
 
     total = (sum(counts) if use_pg else n) * args.steps
     value = total / dt
@@ -415,9 +463,9 @@ def main():
                                                   / (peak * 1e12), 4)},
         "stages_ms_per_launch": {s: round(v["ms_per_launch"], 3) for s, v in stages.items()},
         "generate_s": round(t_gen, 2),
-        "gate": "all rounds accept; negative control (one bit-flipped signature per rank) rejects exactly it and "
-                "the next round, first_bad = lowest corrupted round",
     }
+    out["gate"] = "all rounds accept; negative control (one bit-flipped signature per rank) rejects exactly it " \
+                  "and the next round, first_bad = lowest corrupted round" if args.full else "not run (--full runs it)"
     if use_pg:  # what the process group actually initialised (the exchange runs over it)
         devs = [torch.zeros(1, dtype=torch.int64) for _ in range(world)]
         if args.dist_backend == "gloo":
@@ -427,12 +475,12 @@ def main():
                        "exchange": "one all_reduce(SUM) of %d int64 words: the verdict bitmap at global bit "
                                    "positions (disjoint bits: SUM = OR) + %d first-bad-round slots"
                                    % ((sum(counts) + 63) // 64 + world, world),
-                       "gate": "passed"}
+                       "gate": "passed" if args.full else "not run (--full runs it)"}
         if args.dist_backend == "gloo":
             out["dist"]["devices"] = [int(d) for d in devs]
             if len({int(d) for d in devs}) < world:
                 out["dist"]["note"] = "ranks share a GPU: a correctness run of the N-rank path, not a scaling number"
-    if rank == 0 and world == 1 and args.cpu_per_worker > 0 and not strong:  # CPU baseline: rank 0 at N=1 only
+    if args.full and rank == 0 and world == 1 and args.cpu_per_worker > 0 and not strong:  # CPU baseline: N=1 only
         # bounded sample of the same workload: the first whole segments of the rank-0 shard
         cores, host = host_cores()
         workers = args.cpu_workers or cores

@@ -7,7 +7,7 @@
 #   tests            pytest -m gpu (the whole GPU suite)
 #   tests:EXPR       pytest -m gpu -k EXPR
 #   smoke            __graft_entry__.smoke() (no torch in the process) + the plain-C ABI harness
-#   bench            default bench.py (configs[1], cpu_baseline)
+#   bench            bench.py --full (configs[1], correctness gate, cpu_baseline)
 #   fuzz10, fuzz:N   tests/test_gpu_fuzz.py with DRAND_AMD_FUZZ_SCALE=10 / N (that many times the random cases)
 #   bench2           bench.py --gpus 2 --dist-backend gloo, weak and strong (two ranks on one GPU)
 #   prof             rocprofv3 --kernel-trace --stats of bench.py with BLSV_SERIAL_STAGES=1
@@ -33,7 +33,7 @@ shift
 O=gpurun_out/$TAG
 mkdir -p "$O"
 PYT="python -u -m pytest tests -x -v -m gpu --timeout 300 --timeout-method thread"
-B262="python3 -u bench.py --n 262144 --steps 1 --warmup 0 --cpu-per-worker 0"
+B262="python3 -u bench.py --full --n 262144 --steps 1 --warmup 0 --cpu-per-worker 0"
 rc=0
 for step in "$@"; do
   echo "[gpu.sh] $step $(date +%T)"
@@ -42,15 +42,15 @@ for step in "$@"; do
     tests:*) timeout -k 10 900 $PYT -k "${step#tests:}" > "$O/pytest_gpu_k.log" 2>&1 || rc=12 ;;
     smoke)
       timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.log" 2>&1 || rc=11 ;;
-    bench) timeout -k 10 400 python -u bench.py > "$O/bench.json" 2> "$O/bench.err" || rc=13 ;;
+    bench) timeout -k 10 400 python -u bench.py --full > "$O/bench.json" 2> "$O/bench.err" || rc=13 ;;
     fuzz10|fuzz:*)
       F=10; [ "$step" != fuzz10 ] && F=${step#fuzz:}
       DRAND_AMD_FUZZ_SCALE=$F timeout -k 10 1100 python -u -m pytest tests/test_gpu_fuzz.py -x -v -m gpu -s \
         --timeout 1000 --timeout-method thread > "$O/pytest_gpu_fuzz_x$F.log" 2>&1 || rc=16 ;;
     bench2)
-      timeout -k 10 300 python -u bench.py --gpus 2 --dist-backend gloo --n 262144 --steps 2 --warmup 1 \
+      timeout -k 10 300 python -u bench.py --full --gpus 2 --dist-backend gloo --n 262144 --steps 2 --warmup 1 \
         --cpu-per-worker 0 > "$O/bench2_weak.json" 2> "$O/bench2_weak.err" &&
-      timeout -k 10 300 python -u bench.py --gpus 2 --dist-backend gloo --total-rounds 524291 --steps 2 \
+      timeout -k 10 300 python -u bench.py --full --gpus 2 --dist-backend gloo --total-rounds 524291 --steps 2 \
         --warmup 1 --cpu-per-worker 0 > "$O/bench2_strong.json" 2> "$O/bench2_strong.err" || rc=14 ;;
     prof)
       BLSV_SERIAL_STAGES=1 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof" \
@@ -93,7 +93,7 @@ for step in "$@"; do
       L=variants/libblsverify_$V.so
       if [ ! -f "$L" ]; then echo "no $L"; rc=30; else
         DRAND_AMD_LIB=$L timeout -k 10 900 $PYT > "$O/pytest_gpu_$V.log" 2>&1 &&
-        DRAND_AMD_LIB=$L timeout -k 10 400 python -u bench.py --cpu-per-worker 0 > "$O/bench_$V.json" \
+        DRAND_AMD_LIB=$L timeout -k 10 400 python -u bench.py --full --cpu-per-worker 0 > "$O/bench_$V.json" \
           2> "$O/bench_$V.err" || rc=31
       fi ;;
     vlat:*)
@@ -107,11 +107,11 @@ for step in "$@"; do
       # interleaved same-box A/B: base and each variant, two passes (bench_<name>_<pass>.json)
       IFS=, read -ra VS <<< "${step#ab:}"
       for pass in 1 2; do
-        timeout -k 10 400 python -u bench.py --cpu-per-worker 0 > "$O/bench_base_$pass.json" 2> "$O/bench_base_$pass.err" || { rc=33; break; }
+        timeout -k 10 400 python -u bench.py --full --cpu-per-worker 0 > "$O/bench_base_$pass.json" 2> "$O/bench_base_$pass.err" || { rc=33; break; }
         for V in "${VS[@]}"; do
           L=variants/libblsverify_$V.so
           [ -f "$L" ] || { echo "no $L"; rc=30; break 2; }
-          DRAND_AMD_LIB=$L timeout -k 10 400 python -u bench.py --cpu-per-worker 0 > "$O/bench_${V}_$pass.json" \
+          DRAND_AMD_LIB=$L timeout -k 10 400 python -u bench.py --full --cpu-per-worker 0 > "$O/bench_${V}_$pass.json" \
             2> "$O/bench_${V}_$pass.err" || { rc=33; break 2; }
         done
       done ;;
@@ -119,7 +119,7 @@ for step in "$@"; do
       V=${step#vbench:}
       L=variants/libblsverify_$V.so
       if [ ! -f "$L" ]; then echo "no $L"; rc=30; else
-        DRAND_AMD_LIB=$L timeout -k 10 400 python -u bench.py --cpu-per-worker 0 > "$O/bench_$V.json" \
+        DRAND_AMD_LIB=$L timeout -k 10 400 python -u bench.py --full --cpu-per-worker 0 > "$O/bench_$V.json" \
           2> "$O/bench_$V.err" || rc=31
       fi ;;
     *) echo "unknown step $step"; rc=2 ;;

@@ -21,7 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_two_ranks_one_gpu(mode):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo",
-                        "--steps", "1", "--warmup", "0", "--cpu-per-worker", "0"] + mode,
+                        "--full", "--steps", "1", "--warmup", "0", "--cpu-per-worker", "0"] + mode,
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-3000:])
     recs = [json.loads(x) for x in r.stdout.splitlines() if x.startswith('{"metric"')]

@@ -48,7 +48,7 @@ def test_rccl_world1_exchange_equals_local_verdicts():
 
 def test_bench_force_pg_nccl():
     r = subprocess.run([sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dist-backend", "nccl",
-                        "--force-pg", "--n", "65536", "--steps", "1", "--warmup", "0", "--cpu-per-worker", "0"],
+                        "--force-pg", "--full", "--n", "65536", "--steps", "1", "--warmup", "0", "--cpu-per-worker", "0"],
                        cwd=ROOT, env=_env(), capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-3000:])
     recs = [json.loads(x) for x in r.stdout.splitlines() if x.startswith('{"metric"')]
