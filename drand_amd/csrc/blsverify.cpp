@@ -18,6 +18,7 @@
 #include "../../include/blsverify_testing.h"
 #include "kernels.h"
 #include "engine_ctx.h"
+#include "testops_list.h"
 
 void release_workspace(blsv_ctx* c) {
   for (DBuf* d : {&c->H, &c->HQ, &c->S, &c->F, &c->FW, &c->LN, &c->h_inf, &c->s_inf, &c->cls}) d->release();
@@ -1589,6 +1590,53 @@ int blsv_test_final_exp(blsv_ctx* c, const uint32_t* f, size_t n, uint32_t* out_
   blsk::launch_test_unpack_fp12(dref.as<uint32_t>(), n, dout.as<uint32_t>(), c->stream);
   HIPCHK(c, hipMemcpyAsync(out_ref, dout.p, n * 576, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return BLSV_OK;
+}
+
+static const bls::TestOpInfo* find_test_op(const char* name, int* op) {
+  if (!name) return nullptr;
+  const bls::TestOpInfo* tab = bls::test_op_table();
+  for (int k = 0; k < bls::TOP_COUNT; k++)
+    if (!strcmp(tab[k].name, name)) {
+      if (op) *op = k;
+      return &tab[k];
+    }
+  return nullptr;
+}
+
+int blsv_test_op_info(int index, const char** name, int* in_fp, int* out_fp, int* lanes) {
+  if (index < 0 || index >= bls::TOP_COUNT) return BLSV_EINVAL;
+  const bls::TestOpInfo& t = bls::test_op_table()[index];
+  if (name) *name = t.name;
+  if (in_fp) *in_fp = t.nin;
+  if (out_fp) *out_fp = t.nout;
+  if (lanes) *lanes = t.kind == 3 ? 3 : 1;
+  return BLSV_OK;
+}
+
+int blsv_test_op(blsv_ctx* c, const char* name, const uint32_t* in, size_t n, uint32_t* out) {
+  int op = 0;
+  const bls::TestOpInfo* t = find_test_op(name, &op);
+  if (!c || !t || (n && (!in || !out))) return BLSV_EINVAL;
+  if (n > kMaxChunk) return BLSV_EINVAL;
+  if (!n) return BLSV_OK;
+  (void)hipSetDevice(c->device);
+  const size_t in_bytes = n * (size_t)t->nin * 48, out_bytes = n * (size_t)t->nout * 48;
+  DBuf din, dout, dpark;
+  HIPCHK(c, din.ensure(in_bytes));
+  HIPCHK(c, dout.ensure(out_bytes));
+  if (t->kind == 3) HIPCHK(c, dpark.ensure(blsk::TRI_PARK_WORDS(n) * 4));
+  HIPCHK(c, hipMemcpyAsync(din.p, in, in_bytes, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(dout.p, 0xA5, out_bytes, c->stream));  // an item the kernel skips shows
+  const bool ran = t->kind == 2
+                       ? blsk::launch_test_op_mf(op, din.as<uint32_t>(), n, dout.as<uint32_t>(), c->stream)
+                       : blsk::launch_test_op(op, din.as<uint32_t>(), n, dout.as<uint32_t>(),
+                                              t->kind == 3 ? dpark.as<uint32_t>() : nullptr, c->stream);
+  // no fall-back: an op of the list without a kernel is an error
+  if (!ran) return fail(c, BLSV_EINVAL, "test_op: no kernel for this op");
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(out, dout.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return BLSV_OK;
 }

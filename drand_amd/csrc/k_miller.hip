@@ -6,6 +6,7 @@
 // lines pass run at 2 waves/SIMD (256 VGPRs).
 // kilic Engine.AddPair / AddPairInv [ext] via kyber-bls12381 ValidatePairing.
 #include "kcommon.h"
+#include "testops.h"
 
 namespace blsk {
 
@@ -281,6 +282,48 @@ BLS_KERNEL(BLS_WPE_MILLER_TRI) k_miller_f_tri(const uint32_t* LN, const uint8_t*
   }
   A = tri_conj(t, A);
   if (live) tri_store(F, cnt, base + i, t.role, A);
+}
+
+// ------------------------------------------------------------------ raw operation hooks (testops.h kind 2)
+// The f pass's own LDS forms on operands the test chooses (raw words, one item per lane, layout as
+// k_test.hip k_test_op): fp6_mul_lb reads b through mf_get(0..2); fp12_mul_by_line_pair_lds takes f
+// (12 Fp) and the five Fp2 of L (c0.c0, c0.c1, c0.c2, c1.c1, c1.c2) that k_miller_f parks with mf_put.
+template <int OP, int NIN, int NOUT>
+__global__ void __launch_bounds__(TPB) k_test_op_mf(const uint32_t* in, size_t cnt, uint32_t* out) {
+#if BLS_F6_LIN
+  kp_lds_init<16>();
+#endif
+  const size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
+  if (i >= cnt) return;
+  fp x[NIN], r[NOUT];
+#pragma unroll
+  for (int k = 0; k < NIN; k++)
+#pragma unroll
+    for (int w = 0; w < 12; w++) x[k].l[w] = in[(i * NIN + k) * 12 + w];
+  if constexpr (OP == TOP_fp6_mul_lb) {
+#pragma unroll
+    for (int c = 0; c < 3; c++) mf_put(c, t_f2(x, 6 + 2 * c));
+    t_put6(r, 0, fp6_mul_lb(t_f6(x, 0), [](int c) { return mf_get(c); }));
+  } else {
+#pragma unroll
+    for (int c = 0; c < 5; c++) mf_put(c, t_f2(x, 12 + 2 * c));
+    t_put12(r, 0, fp12_mul_by_line_pair_lds(t_f12(x, 0)));
+  }
+#pragma unroll
+  for (int k = 0; k < NOUT; k++)
+#pragma unroll
+    for (int w = 0; w < 12; w++) out[(i * NOUT + k) * 12 + w] = r[k].l[w];
+}
+
+bool launch_test_op_mf(int op, const uint32_t* in, size_t cnt, uint32_t* out, hipStream_t st) {
+  if (op != TOP_fp6_mul_lb && op != TOP_fp12_mul_by_line_pair_lds) return false;
+  if (!cnt) return true;
+  if (op == TOP_fp6_mul_lb)
+    hipLaunchKernelGGL((k_test_op_mf<TOP_fp6_mul_lb, 12, 6>), dim3(grid_for(cnt)), dim3(TPB), 0, st, in, cnt, out);
+  else
+    hipLaunchKernelGGL((k_test_op_mf<TOP_fp12_mul_by_line_pair_lds, 22, 12>), dim3(grid_for(cnt)), dim3(TPB), 0, st, in,
+                       cnt, out);
+  return true;
 }
 
 // ------------------------------------------------------------------ launchers

@@ -112,6 +112,10 @@ void launch_sign(const uint32_t* sk_words, int32_t index, const uint32_t* H, con
 void launch_gen_chained(const uint32_t* sk_words, const ChainedSrc& src, size_t n, uint8_t* sigs_out, hipStream_t st);
 
 // ---- test hooks (k_misc.hip): raw field / group / pairing building blocks
+// raw operation hooks (testops.h): op = a TestOp; in / out = cnt items of nin / nout Fp (12 raw words
+// each); park: TRI_PARK_WORDS(cnt) words for the 3-lane ops. Each returns false for an op it does not hold.
+bool launch_test_op(int op, const uint32_t* in, size_t cnt, uint32_t* out, uint32_t* park, hipStream_t st);
+bool launch_test_op_mf(int op, const uint32_t* in, size_t cnt, uint32_t* out, hipStream_t st);
 void launch_test_fp_mul(const uint32_t* a, const uint32_t* b, size_t cnt, uint32_t* out, hipStream_t st);
 void launch_test_pairing(const uint32_t* p_tab, const uint32_t* q_aff, size_t cnt, uint32_t* out_f, hipStream_t st);
 void launch_test_unpack_g2(const uint32_t* H, size_t cnt, uint32_t* out, hipStream_t st);

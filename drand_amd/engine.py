@@ -66,6 +66,7 @@ class Engine:
         if rc != 0:
             raise EngineError(rc, f"blsv_create(device={device}) failed")
         self._h = h
+        self._ops = None
         self.device = device
 
     # ------------------------------------------------------------------ lifecycle
@@ -346,6 +347,33 @@ class Engine:
         O = (ctypes.c_uint32 * max(n * 12, 1))()
         self._check(self.lib.blsv_test_fp_mul(self._h, A, B, n, O))
         return list(O)[:n * 12]
+
+    def test_ops(self):
+        """{name: (Fp elements in, Fp elements out, lanes per item)} of blsv_test_op."""
+        ops, k = {}, 0
+        name, a, b, c = ctypes.c_char_p(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        while self.lib.blsv_test_op_info(k, ctypes.byref(name), ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)) == 0:
+            ops[name.value.decode()] = (a.value, b.value, c.value)
+            k += 1
+        return ops
+
+    def test_op(self, name, operands):
+        """blsv_test_op: one raw device operation on len(operands) / in_fp items. operands: a flat list
+        of Fp elements as Python integers below 2^384, each standing for its 12 raw words (tower order
+        within an item, items one after the other); returns the raw result elements the same way.
+        Nothing is converted or reduced on the way in or out."""
+        if self._ops is None:
+            self._ops = self.test_ops()
+        nin, nout, _ = self._ops[name]
+        if len(operands) % nin:
+            raise ValueError(f"{name} takes {nin} Fp elements per item")
+        n = len(operands) // nin
+        raw = b"".join(int(v).to_bytes(48, "little") for v in operands)
+        A = (ctypes.c_uint32 * max(len(raw) // 4, 1)).from_buffer_copy(raw if raw else bytes(4))
+        O = (ctypes.c_uint32 * max(n * nout * 12, 1))()
+        self._check(self.lib.blsv_test_op(self._h, name.encode(), A, n, O))
+        ob = bytes(O)
+        return [int.from_bytes(ob[48 * k:48 * k + 48], "little") for k in range(n * nout)]
 
     def test_pairing(self, p_words, q_words):
         n = len(p_words) // 24

@@ -29,6 +29,24 @@ int blsv_test_pairing(blsv_ctx* ctx, const uint32_t* p, const uint32_t* q, size_
  */
 int blsv_test_final_exp(blsv_ctx* ctx, const uint32_t* f, size_t n, uint32_t* out_pipeline, uint32_t* out_ref);
 
+/*
+ * Raw operation hook: one named form of the device field / tower arithmetic (drand_amd/csrc/testops.h
+ * lists them: fp_*, fp2_*, the one-reduction linear forms, fp4_*, fp6_*, fp12_*, the Miller f pass's
+ * LDS forms and the 3-lane tri_* operations) on n items of operands the caller chooses. An item is
+ * in_fp Fp elements in, out_fp out, each 12 little-endian u32 words, in tower order (c0.c0.c0,
+ * c0.c0.c1, c0.c1.c0, ...); in[(i * in_fp + k) * 12 + w]. The words are copied in and out RAW: no
+ * fp_to_mont / fp_from_mont / fp_canon in between, so a word vector w stands for w * R^-1 mod p
+ * (R = 2^392) and the caller picks the representative (v or v + p, a lazy sum, a limb pattern) within
+ * the operand contract of the form. Booleans (fp_is_zero, fp_eq, tri_is_one, the `converged` flag of
+ * fp_inv_bingcd_raw in its second result) come back as word 0 of an Fp-sized result. One item per lane
+ * (64 per workgroup), or three lanes per item, 21 items per wave, for tri_* (lanes = 3), which run
+ * with the LDS table and the park buffer of the production launchers. Results are not checked on
+ * the device; BLSV_EINVAL for an unknown name.
+ * blsv_test_op_info enumerates the ops (index 0 .. until BLSV_EINVAL); needs no context and no device.
+ */
+int blsv_test_op(blsv_ctx* ctx, const char* name, const uint32_t* in, size_t n, uint32_t* out);
+int blsv_test_op_info(int index, const char** name, int* in_fp, int* out_fp, int* lanes);
+
 /* out[i] = H(msg_i) as affine raw words (x.c0, x.c1, y.c0, y.c1; 48 words) + inf flag. */
 int blsv_test_hash_to_g2(blsv_ctx* ctx, const uint8_t* msgs, const uint32_t* msg_lens, size_t n, uint32_t* out,
                          uint8_t* inf);

@@ -11,6 +11,7 @@
 #include "../drand_amd/csrc/pairing.h"
 #include "../drand_amd/csrc/hash.h"
 #include "../drand_amd/csrc/tri.h"
+#include "../drand_amd/csrc/testops.h"
 
 namespace bls {
 unsigned long long g_fp_mul_count = 0;
@@ -419,7 +420,76 @@ static int cmd_f6fuzz(unsigned long n) {
   return bad ? 1 : 0;
 }
 
+// ops: the raw operation hooks of drand_amd/csrc/testops.h on the host build (kind 0: the forms this
+// build contains, KpMad in place of the LDS tables of k p). Reads one item per line from stdin: the op's
+// name, then its operands, each Fp element as 96 hex digits (its twelve 32-bit words, most significant
+// first), raw: nothing is converted or reduced. Prints the raw result elements of each item on one line.
+// `ops list` prints name, Fp in, Fp out, kind of every op instead.
+template <int OP, int NIN, int NOUT, int KIND>
+static bool ops_run_t(const fp* x, fp* r) {
+  if constexpr (KIND == 0) {
+    test_op_run<OP, KpMad>(x, r);
+    return true;
+  } else {
+    return false;
+  }
+}
+static bool ops_run(int op, const fp* x, fp* r) {
+  switch (op) {
+#define X(name, nin, nout, kind) \
+  case TOP_##name:               \
+    return ops_run_t<TOP_##name, nin, nout, kind>(x, r);
+    BLS_TEST_OPS(X)
+#undef X
+  }
+  return false;
+}
+static int cmd_ops(bool list) {
+  const TestOpInfo* tab = test_op_table();
+  if (list) {
+    for (int k = 0; k < TOP_COUNT; k++) printf("%s %d %d %d\n", tab[k].name, tab[k].nin, tab[k].nout, tab[k].kind);
+    return 0;
+  }
+  static char line[64 + 24 * 97 + 8];
+  unsigned long lineno = 0;
+  while (fgets(line, sizeof line, stdin)) {
+    lineno++;
+    char* save = nullptr;
+    const char* name = strtok_r(line, " \n", &save);
+    if (!name) continue;
+    int op = -1;
+    for (int k = 0; k < TOP_COUNT; k++)
+      if (!strcmp(tab[k].name, name)) op = k;
+    if (op < 0 || tab[op].kind != 0) {
+      fprintf(stderr, "ops: line %lu: no host op '%s'\n", lineno, name);
+      return 2;
+    }
+    fp x[24], r[12];
+    for (int k = 0; k < tab[op].nin; k++) {
+      const char* tok = strtok_r(nullptr, " \n", &save);
+      if (!tok || strlen(tok) != 96) {
+        fprintf(stderr, "ops: line %lu: operand %d is not 96 hex digits\n", lineno, k);
+        return 2;
+      }
+      for (int w = 0; w < 12; w++) {
+        char b[9];
+        memcpy(b, tok + 8 * (11 - w), 8);
+        b[8] = 0;
+        x[k].l[w] = (uint32_t)strtoul(b, nullptr, 16);
+      }
+    }
+    if (!ops_run(op, x, r)) return 2;
+    for (int k = 0; k < tab[op].nout; k++) {
+      if (k) putchar(' ');
+      for (int w = 11; w >= 0; w--) printf("%08x", r[k].l[w]);
+    }
+    putchar('\n');
+  }
+  return 0;
+}
+
 int main(int argc, char** argv) {
+  if (argc >= 2 && !strcmp(argv[1], "ops")) return cmd_ops(argc == 3 && !strcmp(argv[2], "list"));
   if (argc == 3 && !strcmp(argv[1], "hash")) return cmd_hash(argv[2]);
   if (argc == 3 && !strcmp(argv[1], "powfuzz")) return cmd_powfuzz(strtoul(argv[2], nullptr, 10));
   if (argc == 3 && !strcmp(argv[1], "invfuzz")) return cmd_invfuzz(strtoul(argv[2], nullptr, 10));
