@@ -99,6 +99,14 @@ SIGNATURES = {
     "blsv_service_verify_recovered": (ctypes.c_int, [vp, u8p, u8p, sz, u8p, u8p, u8p]),
     "blsv_service_stats": (ctypes.c_int, [vp, u64p, u64p, u64p]),
     "blsv_test_service_limits": (ctypes.c_int, [vp, sz, sz, sz, u64p]),
+    "blsv_verify_chained_rlc": (ctypes.c_int, [vp, ctypes.c_uint64, u8p, sz, u8p, sz, u8p, u64p, u8p]),
+    "blsv_verify_unchained_rlc": (ctypes.c_int, [vp, u64p, ctypes.c_uint64, u8p, sz, u8p, u64p, u8p]),
+    "blsv_verify_chained_rlc_dev": (ctypes.c_int, [vp, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, vp, sz, vp,
+                                                    sz, vp, vp, vp, vp]),
+    "blsv_set_rlc_group": (sz, [vp, sz]),
+    "blsv_rlc_stats": (ctypes.c_int, [vp, u64p, u64p, u64p]),
+    "blsv_test_rlc_seed": (ctypes.c_int, [vp, u8p]),
+    "blsv_test_rlc_sums": (ctypes.c_int, [vp, ctypes.c_uint64, u8p, sz, u8p, sz, u8p, u8p]),
 }
 
 _lib = None

@@ -84,9 +84,13 @@ def randomness_from_signature(sig: bytes) -> bytes:
     return hashlib.sha256(sig).digest()
 
 
-def _verify_run(engine, first_round, prev0, sigs):
+def _verify_run(engine, first_round, prev0, sigs, fast=False):
     """Verify ``sigs`` as consecutive rounds starting at ``first_round`` whose first previous
     signature is ``prev0``. Returns the index of the first rejected beacon, or None.
+
+    ``fast=True`` hands the range to ``Engine.verify_chained_rlc`` (opt-in randomized batch
+    verification: same rejects, acceptance of a bad round with probability at most 2^-64,
+    include/blsverify.h); the default is the exact check.
 
     A wrong-length signature is a reject in the reference (kyber's unmarshal fails); the engine
     refuses such input host-side, so the run is cut there and that index is reported."""
@@ -100,10 +104,11 @@ def _verify_run(engine, first_round, prev0, sigs):
                                        [sigs[0]])
         if not first.ok[0]:
             return 0
-        rest = _verify_run(engine, first_round + 1, sigs[0], sigs[1:cut])
+        rest = _verify_run(engine, first_round + 1, sigs[0], sigs[1:cut], fast)
         return None if rest is None else rest + 1
     if cut:
-        res = engine.verify_chained(first_round, bytes(prev0), [bytes(s) for s in sigs[:cut]])
+        run = engine.verify_chained_rlc if fast else engine.verify_chained
+        res = run(first_round, bytes(prev0), [bytes(s) for s in sigs[:cut]])
         if res.first_bad is not None:
             return res.first_bad - first_round
     return None if cut == n else cut
@@ -119,10 +124,14 @@ class VerifyingClient:
     ``point_of_trust`` is ``WithVerifiedResult`` (client/client.go options; verify_test.go:19 seeds it
     with round 1). Reference quirk kept as is: without one, or for a round below it, the walk
     restarts at round 1 with ``GroupHash`` as the trusted signature (verify.go:131-137), so round 2
-    is checked against ``Message(2, GroupHash)`` and rejects on a real chain."""
+    is checked against ``Message(2, GroupHash)`` and rejects on a real chain.
+
+    ``fast=True`` verifies the walked ranges with the randomized batch verification (see
+    ``_verify_run``); the requested round itself is one beacon and always takes the exact check."""
 
     def __init__(self, engine, info: ChainInfo, get: Callable[[int], RandomData], strict=False,
-                 v2from=UINT64_MAX, chunk=1 << 16, point_of_trust: Optional[RandomData] = None):
+                 v2from=UINT64_MAX, chunk=1 << 16, point_of_trust: Optional[RandomData] = None, fast=False):
+        self.fast = bool(fast)
         self.engine = engine
         self.info = info
         self.get = get
@@ -156,7 +165,7 @@ class VerifyingClient:
                     fetch_err = FetchError(r, e)
                     break
             sigs = [res.sig() for res in results]
-            bad = _verify_run(self.engine, lo, trust_prev, sigs)
+            bad = _verify_run(self.engine, lo, trust_prev, sigs, self.fast)
             if bad is not None:
                 raise VerifyError(lo + bad, f"verifying beacon: round {lo + bad}: bls: invalid signature")
             if fetch_err is not None:
@@ -201,7 +210,7 @@ class SyncOutcome:
 
 
 def sync_chain(engine, public_key: bytes, last: Beacon, packets: Iterable[Beacon], up_to: int,
-               put: Callable[[Beacon], None], chunk=1 << 16) -> SyncOutcome:
+               put: Callable[[Beacon], None], chunk=1 << 16, fast=False) -> SyncOutcome:
     """Batched ``syncer.tryNode`` + ``appendStore.Put`` over one GPU engine.
 
     Per chunk of the stream: the longest prefix that links (``Round == last.Round+1`` and
@@ -209,7 +218,8 @@ def sync_chain(engine, public_key: bytes, last: Beacon, packets: Iterable[Beacon
     Beacons are stored in order up to the first failure, exactly where the serial loop would stop
     (verify before Put, sync.go:105-113). The first unlinked beacon is verified on its own so the
     stop reason matches the reference's (a bad signature is reported before a linkage error).
-    Unlike the serial loop, up to ``chunk`` packets are read from the stream ahead of the verify."""
+    Unlike the serial loop, up to ``chunk`` packets are read from the stream ahead of the verify.
+    ``fast=True`` verifies each linked range with the randomized batch verification (``_verify_run``)."""
     engine.set_public_key(public_key)
     stored = 0
     it = iter(packets)
@@ -230,7 +240,8 @@ def sync_chain(engine, public_key: bytes, last: Beacon, packets: Iterable[Beacon
             prev_r, prev_s = b.round, b.signature
         bad = None
         if linked:
-            bad = _verify_run(engine, batch[0].round, batch[0].previous_sig, [b.signature for b in batch[:linked]])
+            bad = _verify_run(engine, batch[0].round, batch[0].previous_sig, [b.signature for b in batch[:linked]],
+                              fast)
         ok_upto = linked if bad is None else bad
         for b in batch[:ok_upto]:
             try:

@@ -2,6 +2,7 @@
 // Every verdict is computed by the device kernels (kernels.h); this file only moves bytes, sequences
 // launches and does the reference's control-flow bookkeeping (share selection order, index parsing).
 #include <hip/hip_runtime.h>
+#include <sys/random.h>
 
 #include <algorithm>
 #include <initializer_list>
@@ -490,6 +491,153 @@ static int verify_driver(blsv_ctx* c, size_t n, const uint8_t* d_sigs, size_t st
 }
 
 static PkSel group_pk(blsv_ctx* c) { return {c->commits.as<uint32_t>(), c->commit_inf.as<uint8_t>(), nullptr}; }
+
+// ---------------------------------------------------------------- randomized batch verification
+// blsv_verify_*_rlc (include/blsverify.h, rlc.h): per pass the head as usual, then the combination
+// stage, one pairing check per group with the existing Miller and final-exponentiation stages, and the
+// exact stages again on the items of every group whose check failed.
+static bool use_rlc(const blsv_ctx* c, size_t n) { return n > c->lat_max && n >= 2 * c->rlc.group; }
+
+// the call's seed as eight big-endian words: fresh from the OS CSPRNG unless a test pinned one
+static int rlc_draw_seed(blsv_ctx* c, uint32_t (&w)[8]) {
+  uint8_t s[32];
+  if (c->rlc.seed_pinned) {
+    memcpy(s, c->rlc.seed, 32);
+  } else {
+    size_t got = 0;
+    while (got < sizeof s) {
+      const ssize_t r = getrandom(s + got, sizeof s - got, 0);
+      if (r < 0 && errno == EINTR) continue;
+      if (r <= 0) return fail(c, BLSV_EHIP, "rlc: getrandom failed: %s", strerror(errno));
+      got += (size_t)r;
+    }
+  }
+  for (int k = 0; k < 8; k++)
+    w[k] = ((uint32_t)s[4 * k] << 24) | ((uint32_t)s[4 * k + 1] << 16) | ((uint32_t)s[4 * k + 2] << 8) | s[4 * k + 3];
+  return BLSV_OK;
+}
+
+static size_t round64(size_t v) { return (std::max(v, size_t(1)) + 63) & ~size_t(63); }
+
+// the combination stage of one pass into the group staging (ng slots)
+static int rlc_sums(blsv_ctx* c, size_t base, size_t cnt, const uint32_t (&seed)[8], hipStream_t st) {
+  rlc_state& r = c->rlc;
+  const size_t ng = blsk::rlc_groups(cnt, r.group), cap = round64(ng);
+  HIPCHK(c, r.part.ensure(2 * blsk::kRlcPartWords * blsk::rlc_lanes(cnt) * 4));
+  HIPCHK(c, r.gH.ensure(cap * blsk::H_WORDS * 4));
+  HIPCHK(c, r.gS.ensure(cap * blsk::S_WORDS * 4));
+  HIPCHK(c, r.g_hinf.ensure(cap));
+  HIPCHK(c, r.g_sinf.ensure(cap));
+  HIPCHK(c, r.gcls.ensure(cap));
+  StageTimer tm(c, ST_RLC, cnt, st);
+  blsk::launch_rlc_sums(c->H.as<uint32_t>(), c->h_inf.as<uint8_t>(), c->S.as<uint32_t>(), c->s_inf.as<uint8_t>(),
+                        c->cls.as<uint8_t>(), cnt, base, seed, r.group, r.part.as<uint32_t>(), r.gH.as<uint32_t>(),
+                        r.g_hinf.as<uint8_t>(), r.gS.as<uint32_t>(), r.g_sinf.as<uint8_t>(), st);
+  return BLSV_OK;
+}
+
+// Miller + final exponentiation of `cnt` staged items with the group key (F, FW, LN are the pass's own:
+// nothing of the pass is in them at this point, and cnt never exceeds the pass)
+static void rlc_pairing_check(blsv_ctx* c, const uint32_t* H, const uint8_t* h_inf, const uint32_t* S,
+                              const uint8_t* s_inf, uint8_t* cls, size_t cnt, hipStream_t st) {
+  const PkSel pk = group_pk(c);
+  {
+    StageTimer tm(c, ST_MILLER, cnt, st);
+    blsk::launch_miller(pk.tab, pk.inf, pk.idx, H, h_inf, S, s_inf, cls, cnt, c->F.as<uint32_t>(),
+                        c->LN.as<uint32_t>(), std::min(cnt, kLineSub), c->FW.as<uint32_t>(), st);
+  }
+  StageTimer tm(c, ST_FEXP, cnt, st);
+  blsk::launch_final_exp(c->F.as<uint32_t>(), c->FW.as<uint32_t>(), cnt, cls, st, c->LN.as<uint32_t>());
+}
+
+// Stages 3..5 of one pass on the randomized path, after run_head. Synchronises st once (the group
+// verdicts decide what the exact stages run on).
+static int run_tail_rlc(blsv_ctx* c, size_t base, size_t cnt, const uint32_t (&seed)[8], uint64_t* d_bitmap,
+                        unsigned long long* d_first_bad, uint8_t* d_cls_out, hipStream_t st, uint64_t label0 = 0) {
+  rlc_state& r = c->rlc;
+  const size_t G = r.group, ng = blsk::rlc_groups(cnt, G);
+  int rc = rlc_sums(c, base, cnt, seed, st);
+  if (rc) return rc;
+  HIPCHK(c, hipMemsetAsync(r.gcls.p, 0, ng, st));
+  rlc_pairing_check(c, r.gH.as<uint32_t>(), r.g_hinf.as<uint8_t>(), r.gS.as<uint32_t>(), r.g_sinf.as<uint8_t>(),
+                    r.gcls.as<uint8_t>(), ng, st);
+  HIPCHK(c, hipGetLastError());
+  // sized once for the largest pass and the smallest group: never reallocated under a copy in flight
+  HIPCHK(c, r.host.ensure(kMaxChunk / kRlcGroupMin * 5 + 16));
+  uint8_t* verdict = r.host.as<uint8_t>();
+  HIPCHK(c, hipMemcpyAsync(verdict, r.gcls.p, ng, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  uint32_t* fail_list = reinterpret_cast<uint32_t*>(verdict + ((ng + 7) & ~size_t(7)));
+  size_t nf = 0;
+  for (size_t g = 0; g < ng; g++)
+    if (verdict[g] != BLSV_REJ_OK) fail_list[nf++] = (uint32_t)g;
+  r.groups += ng;
+  r.groups_failed += nf;
+  if (nf) {
+    // ascending, so only the last entry can be the pass's short last group
+    const size_t m = nf * G - (fail_list[nf - 1] == ng - 1 ? ng * G - cnt : 0), cap = round64(m);
+    r.items_exact += m;
+    HIPCHK(c, r.fail.ensure(nf * 4));
+    HIPCHK(c, r.cH.ensure(cap * blsk::H_WORDS * 4));
+    HIPCHK(c, r.cS.ensure(cap * blsk::S_WORDS * 4));
+    HIPCHK(c, r.c_hinf.ensure(cap));
+    HIPCHK(c, r.c_sinf.ensure(cap));
+    HIPCHK(c, r.ccls.ensure(cap));
+    HIPCHK(c, hipMemcpyAsync(r.fail.p, fail_list, nf * 4, hipMemcpyHostToDevice, st));
+    {
+      StageTimer tm(c, ST_RLC, m, st);
+      blsk::launch_rlc_gather(r.fail.as<uint32_t>(), G, m, c->H.as<uint32_t>(), c->h_inf.as<uint8_t>(),
+                              c->S.as<uint32_t>(), c->s_inf.as<uint8_t>(), c->cls.as<uint8_t>(), cnt,
+                              r.cH.as<uint32_t>(), r.c_hinf.as<uint8_t>(), r.cS.as<uint32_t>(), r.c_sinf.as<uint8_t>(),
+                              r.ccls.as<uint8_t>(), st);
+    }
+    rlc_pairing_check(c, r.cH.as<uint32_t>(), r.c_hinf.as<uint8_t>(), r.cS.as<uint32_t>(), r.c_sinf.as<uint8_t>(),
+                      r.ccls.as<uint8_t>(), m, st);
+    StageTimer tm(c, ST_RLC, m, st);
+    blsk::launch_rlc_scatter(r.fail.as<uint32_t>(), G, m, r.ccls.as<uint8_t>(), c->cls.as<uint8_t>(), cnt, st);
+  }
+  {
+    StageTimer tm(c, ST_FINISH, cnt, st);
+    blsk::launch_finish(c->cls.as<uint8_t>(), base, cnt, d_bitmap, d_first_bad, label0, st);
+  }
+  if (d_cls_out) HIPCHK(c, hipMemcpyAsync(d_cls_out + base, c->cls.p, cnt, hipMemcpyDeviceToDevice, st));
+  HIPCHK(c, hipGetLastError());
+  // (the next pass writes r.host's list of failing groups only after its own synchronisation of st,
+  // which this pass's upload of the list precedes)
+  return BLSV_OK;
+}
+
+// verify_driver's pipeline with the randomized tail (the caller checked use_rlc)
+template <typename HashFn>
+static int verify_driver_rlc(blsv_ctx* c, size_t n, const uint8_t* d_sigs, HashFn hash, uint8_t* ok_bitmap,
+                             uint64_t* first_bad_idx, uint8_t* reject_class) {
+  const size_t words = (n + 63) / 64;
+  int rc = ensure_workspace(c, n);
+  if (rc) return rc;
+  uint32_t seed[8];
+  rc = rlc_draw_seed(c, seed);
+  if (rc) return rc;
+  HIPCHK(c, c->bitmap.ensure(words * 8 + 8));
+  HIPCHK(c, c->first_bad.ensure(8));
+  HIPCHK(c, hipMemsetAsync(c->first_bad.p, 0xff, 8, c->stream));
+  if (reject_class) HIPCHK(c, c->misc.ensure(n + 64));
+  for (size_t base = 0; base < n; base += c->cap) {
+    const size_t cnt = std::min(c->cap, n - base);
+    rc = run_head(c, d_sigs, 96, 0, base, cnt, c->stream, [&]() { hash(base, cnt); });
+    if (rc) return rc;
+    rc = run_tail_rlc(c, base, cnt, seed, c->bitmap.as<uint64_t>(), c->first_bad.as<unsigned long long>(),
+                      reject_class ? c->misc.as<uint8_t>() : nullptr, c->stream);
+    if (rc) return rc;
+  }
+  std::vector<uint64_t> w(words + 1, 0);
+  uint64_t fb = UINT64_MAX;
+  HIPCHK(c, download_sync(c, {{w.data(), c->bitmap.p, words * 8},
+                              {&fb, c->first_bad.p, 8},
+                              {reject_class, c->misc.p, reject_class ? n : 0}}));
+  if (ok_bitmap) bitmap_words_to_bytes(w, n, ok_bitmap);
+  if (first_bad_idx) *first_bad_idx = fb;
+  return BLSV_OK;
+}
 
 // decode one 48-byte G1 point into (tab, inf) entry 0 on device; returns class via *cls
 static int decode_g1(blsv_ctx* c, const uint8_t* pk48, size_t cnt, DBuf& tab, DBuf& inf, std::vector<uint8_t>& cls) {
@@ -1427,6 +1575,162 @@ int blsv_generate_chained_dev(blsv_ctx* c, const uint8_t* sk32, uint64_t first_r
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(st));  // sk staging buffer is reused by later calls
   return BLSV_OK;
+}
+
+// ------------------------------------------------------------------ randomized batch verification
+int blsv_verify_chained_rlc(blsv_ctx* c, uint64_t first_round, const uint8_t* prev0, size_t prev0_len,
+                            const uint8_t* sigs96, size_t n, uint8_t* ok_bitmap, uint64_t* first_bad,
+                            uint8_t* reject_class) {
+  if (!c) return BLSV_EINVAL;
+  if (!use_rlc(c, n))
+    return blsv_verify_chained(c, first_round, prev0, prev0_len, sigs96, n, ok_bitmap, first_bad, reject_class);
+  if (!c->has_group) return fail(c, BLSV_ENOGROUP, "verify_chained_rlc: no group key set");
+  if (!sigs96 || !prev0 || (prev0_len != 32 && prev0_len != 96))
+    return fail(c, BLSV_EINVAL, "verify_chained_rlc: prev0 must be 32 or 96 bytes");
+  if (n > SIZE_MAX / 96 - 1) return fail(c, BLSV_EINVAL, "verify_chained_rlc: %zu rounds overflow the byte count", n);
+  (void)hipSetDevice(c->device);
+  HIPCHK(c, c->in_sigs.ensure(n * 96 + 96));
+  HIPCHK(c, c->seeds.ensure(96));
+  HIPCHK(c, h2d(c, c->in_sigs.p, sigs96, n * 96));
+  HIPCHK(c, h2d(c, c->seeds.p, prev0, prev0_len));
+  blsk::ChainedSrc src{c->in_sigs.as<uint8_t>(), c->seeds.as<uint8_t>(), first_round, n, (uint32_t)prev0_len};
+  uint64_t fb = UINT64_MAX;
+  int rc = verify_driver_rlc(
+      c, n, c->in_sigs.as<uint8_t>(),
+      [&](size_t base, size_t cnt) {
+        blsk::launch_hash_chained(src, base, cnt, c->H.as<uint32_t>(), c->h_inf.as<uint8_t>(), c->HQ.as<uint32_t>(),
+                                  c->stream);
+      },
+      ok_bitmap, &fb, reject_class);
+  if (rc) return rc;
+  if (first_bad) *first_bad = fb == UINT64_MAX ? UINT64_MAX : first_round + fb;
+  return BLSV_OK;
+}
+
+int blsv_verify_unchained_rlc(blsv_ctx* c, const uint64_t* rounds, uint64_t first_round, const uint8_t* sigs96,
+                              size_t n, uint8_t* ok_bitmap, uint64_t* first_bad, uint8_t* reject_class) {
+  if (!c) return BLSV_EINVAL;
+  if (!use_rlc(c, n)) return blsv_verify_unchained(c, rounds, first_round, sigs96, n, ok_bitmap, first_bad, reject_class);
+  if (!c->has_group) return fail(c, BLSV_ENOGROUP, "verify_unchained_rlc: no group key set");
+  if (!sigs96) return fail(c, BLSV_EINVAL, "verify_unchained_rlc: null signatures");
+  (void)hipSetDevice(c->device);
+  HIPCHK(c, c->in_sigs.ensure(n * 96 + 96));
+  HIPCHK(c, h2d(c, c->in_sigs.p, sigs96, n * 96));
+  const uint64_t* d_rounds = nullptr;
+  if (rounds) {
+    HIPCHK(c, c->in_rounds.ensure(n * 8));
+    HIPCHK(c, h2d(c, c->in_rounds.p, rounds, n * 8));
+    d_rounds = c->in_rounds.as<uint64_t>();
+  }
+  uint64_t fb = UINT64_MAX;
+  int rc = verify_driver_rlc(
+      c, n, c->in_sigs.as<uint8_t>(),
+      [&](size_t base, size_t cnt) {
+        blsk::launch_hash_unchained(d_rounds, first_round, base, cnt, c->H.as<uint32_t>(), c->h_inf.as<uint8_t>(),
+                                    c->HQ.as<uint32_t>(), c->stream);
+      },
+      ok_bitmap, &fb, reject_class);
+  if (rc) return rc;
+  if (first_bad) *first_bad = fb == UINT64_MAX ? UINT64_MAX : (rounds ? rounds[fb] : first_round + fb);
+  return BLSV_OK;
+}
+
+int blsv_verify_chained_rlc_dev(blsv_ctx* c, uint64_t first_round, uint64_t seg_len, uint64_t seg_phase,
+                                const uint8_t* d_seeds96, size_t seed0_len, const uint8_t* d_sigs96, size_t n,
+                                uint64_t* d_bitmap, uint64_t* d_first_bad, uint8_t* d_reject_class, void* stream) {
+  if (!c) return BLSV_EINVAL;
+  if (!use_rlc(c, n))
+    return blsv_verify_chained_dev(c, first_round, seg_len, seg_phase, d_seeds96, seed0_len, d_sigs96, n, d_bitmap,
+                                   d_first_bad, d_reject_class, stream);
+  if (!c->has_group) return fail(c, BLSV_ENOGROUP, "verify_chained_rlc_dev: no group key set");
+  if (!d_seeds96 || !d_sigs96 || !d_bitmap || !d_first_bad || (seed0_len != 32 && seed0_len != 96))
+    return fail(c, BLSV_EINVAL, "verify_chained_rlc_dev: bad arguments");
+  if (seg_phase && (!seg_len || seg_phase >= seg_len))
+    return fail(c, BLSV_EINVAL, "verify_chained_rlc_dev: seg_phase must be < seg_len");
+  (void)hipSetDevice(c->device);
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  uint32_t seed[8];
+  int rc = rlc_draw_seed(c, seed);
+  if (rc) return rc;
+  HIPCHK(c, hipMemsetAsync(d_first_bad, 0xff, 8, st));
+  rc = ensure_workspace(c, n);
+  if (rc) return rc;
+  blsk::ChainedSrc src{d_sigs96, d_seeds96, first_round, seg_len ? seg_len : n, (uint32_t)seed0_len, seg_phase};
+  for (size_t base = 0; base < n; base += c->cap) {
+    const size_t cnt = std::min(c->cap, n - base);
+    rc = run_head(c, d_sigs96, 96, 0, base, cnt, st, [&]() {
+      blsk::launch_hash_chained(src, base, cnt, c->H.as<uint32_t>(), c->h_inf.as<uint8_t>(), c->HQ.as<uint32_t>(), st);
+    });
+    if (rc) return rc;
+    rc = run_tail_rlc(c, base, cnt, seed, d_bitmap, (unsigned long long*)d_first_bad, d_reject_class, st, first_round);
+    if (rc) return rc;
+  }
+  return BLSV_OK;
+}
+
+size_t blsv_set_rlc_group(blsv_ctx* c, size_t g) {
+  if (!c) return 0;
+  const size_t prev = c->rlc.group;
+  size_t v = kRlcGroupMin;
+  while (v * 2 <= g && v < kRlcGroupMax) v *= 2;
+  c->rlc.group = v;
+  return prev;
+}
+
+int blsv_rlc_stats(blsv_ctx* c, uint64_t* groups, uint64_t* groups_failed, uint64_t* items_exact) {
+  if (!c) return BLSV_EINVAL;
+  if (groups) *groups = c->rlc.groups;
+  if (groups_failed) *groups_failed = c->rlc.groups_failed;
+  if (items_exact) *items_exact = c->rlc.items_exact;
+  return BLSV_OK;
+}
+
+int blsv_test_rlc_seed(blsv_ctx* c, const uint8_t* seed32) {
+  if (!c) return BLSV_EINVAL;
+  c->rlc.seed_pinned = seed32 != nullptr;
+  if (seed32) memcpy(c->rlc.seed, seed32, 32);
+  return BLSV_OK;
+}
+
+int blsv_test_rlc_sums(blsv_ctx* c, uint64_t first_round, const uint8_t* prev0, size_t prev0_len,
+                       const uint8_t* sigs96, size_t n, uint8_t* out_a96, uint8_t* out_b96) {
+  if (!c) return BLSV_EINVAL;
+  if (!n || !sigs96 || !prev0 || !out_a96 || !out_b96 || (prev0_len != 32 && prev0_len != 96))
+    return fail(c, BLSV_EINVAL, "test_rlc_sums: bad arguments");
+  (void)hipSetDevice(c->device);
+  uint32_t seed[8];
+  int rc = rlc_draw_seed(c, seed);
+  if (rc) return rc;
+  rc = ensure_workspace(c, n);
+  if (rc) return rc;
+  HIPCHK(c, c->in_sigs.ensure(n * 96 + 96));
+  HIPCHK(c, c->seeds.ensure(96));
+  HIPCHK(c, h2d(c, c->in_sigs.p, sigs96, n * 96));
+  HIPCHK(c, h2d(c, c->seeds.p, prev0, prev0_len));
+  blsk::ChainedSrc src{c->in_sigs.as<uint8_t>(), c->seeds.as<uint8_t>(), first_round, n, (uint32_t)prev0_len};
+  rlc_state& r = c->rlc;
+  size_t done = 0;  // groups written so far
+  for (size_t base = 0; base < n; base += c->cap) {
+    const size_t cnt = std::min(c->cap, n - base), ng = blsk::rlc_groups(cnt, r.group);
+    rc = run_head(c, c->in_sigs.as<uint8_t>(), 96, 0, base, cnt, c->stream, [&]() {
+      blsk::launch_hash_chained(src, base, cnt, c->H.as<uint32_t>(), c->h_inf.as<uint8_t>(), c->HQ.as<uint32_t>(),
+                                c->stream);
+    });
+    if (rc) return rc;
+    rc = rlc_sums(c, base, cnt, seed, c->stream);
+    if (rc) return rc;
+    HIPCHK(c, r.out96.ensure(2 * ng * 96));
+    uint8_t* d_out = r.out96.as<uint8_t>();
+    blsk::launch_rlc_compress(r.gH.as<uint32_t>(), r.g_hinf.as<uint8_t>(), ng, d_out, c->stream);
+    blsk::launch_rlc_compress(r.gS.as<uint32_t>(), r.g_sinf.as<uint8_t>(), ng, d_out + ng * 96, c->stream);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out_a96 + done * 96, d_out, ng * 96, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out_b96 + done * 96, d_out + ng * 96, ng * 96, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->io_up_off = 0;
+    done += ng;
+  }
+  return (int)done;
 }
 
 // ------------------------------------------------------------------ stage profiling

@@ -93,7 +93,18 @@ struct PinBuf {
 using namespace blsv_detail;
 
 // Stage timing (blsv_profile_*): HIP events recorded around every stage launch on the launch stream.
-enum Stage { ST_HASH = 0, ST_DECOMP = 1, ST_MILLER = 2, ST_FEXP = 3, ST_FINISH = 4, ST_LAT = 5, ST_N = 6 };
+// ST_RLC: the randomized path's combination stage with its gather / scatter (blsv_verify_*_rlc); that
+// path's group checks and exact fallback are timed as ST_MILLER / ST_FEXP launches of their own.
+enum Stage {
+  ST_HASH = 0,
+  ST_DECOMP = 1,
+  ST_MILLER = 2,
+  ST_FEXP = 3,
+  ST_FINISH = 4,
+  ST_LAT = 5,
+  ST_RLC = 6,
+  ST_N = 7
+};
 struct ProfRec {
   int stage;
   size_t items;
@@ -104,6 +115,12 @@ struct ProfRec {
 // of at most this many items runs on the latency path. BLSV_LAT_MAX overrides it (0 = batch pipeline
 // only). Any value is clamped to kMaxChunk: the latency kernels write one class byte per item into the
 // chunk-sized class buffer, so a larger batch always takes the chunked pipeline.
+// Randomized batch verification (rlc.h): items per shared pairing check. blsv_set_rlc_group rounds to a
+// power of two in [kRlcGroupMin, kRlcGroupMax]. Default from profiles/rlc_bench.json (1M rounds, ms per
+// step at G = 32 / 64 / 256 / 1024): all valid 219 / 212 / 212 / 217, one bad round 229 / 222 / 223 / 227,
+// 0.1% bad rounds 236 / 244 / 301 / 433 -- a smaller group's checks cost little, its fallback much less.
+constexpr size_t kRlcGroupDefault = 64;
+constexpr size_t kRlcGroupMin = 8, kRlcGroupMax = 4096;
 constexpr size_t kLatMaxDefault = 1536;  // profiles/r04zk_latency_sweep.json: the paths cross near 1,750
 // Default chunk: BLSV_CHUNK (items, rounded up to a multiple of 64, clamped to [kMinChunk, kMaxChunk]),
 // else kMaxChunk.
@@ -140,6 +157,15 @@ inline size_t lat_max_env() {
   }();
   return v;
 }
+
+struct rlc_state {
+  size_t group = kRlcGroupDefault;
+  bool seed_pinned = false;  // blsv_test_rlc_seed
+  uint8_t seed[32] = {0};
+  uint64_t groups = 0, groups_failed = 0, items_exact = 0;  // blsv_rlc_stats
+  DBuf part, gH, gS, g_hinf, g_sinf, gcls, cH, cS, c_hinf, c_sinf, ccls, fail, out96;
+  PinBuf host;  // group verdicts down, failing group indices up
+};
 
 struct blsv_ctx {
   int device = 0;
@@ -196,6 +222,9 @@ struct blsv_ctx {
   } spec[2];
   uint64_t spec_hits = 0, spec_misses = 0;  // speculative recoveries kept / recomputed
   DBuf arena;
+  // randomized batch verification (blsv_verify_*_rlc, rlc.h): the lanes' partial sums, one H / S slot per
+  // group with flags and class bytes, the compact staging of the exact fallback, the failing groups
+  rlc_state rlc;
 };
 
 #define HIPCHK(ctx, expr)                                                             \

@@ -65,6 +65,29 @@ void launch_final_exp(uint32_t* F, uint32_t* W, size_t cnt, uint8_t* cls, hipStr
 void launch_finish(const uint8_t* cls, size_t base, size_t cnt, uint64_t* bitmap, unsigned long long* first_bad,
                    uint64_t label0, hipStream_t st);
 
+// ---- randomized batch verification (k_rlc.hip, rlc.h): the combination stage of one pass.
+// Groups of `group` consecutive items (a power of two >= kRlcLaneItems; the last may be short); per
+// group A = sum r_i H_i and B = sum r_i S_i over the items with cls == 0 (an item's point at infinity
+// is left out of its own sum only), r_i = first 8 bytes of SHA-256(seed || BE64(index0 + i)). The sums
+// land in affine form in slot g of GH / GS (H / S layout, stride rlc_groups(cnt, group)) with
+// g_hinf / g_sinf. part: 2 * kRlcPartWords * rlc_lanes(cnt) words for the lanes' Jacobian partial sums.
+constexpr size_t kRlcLaneItems = 8;
+constexpr size_t kRlcPartWords = 72;
+constexpr size_t rlc_lanes(size_t cnt) { return (cnt + kRlcLaneItems - 1) / kRlcLaneItems; }
+constexpr size_t rlc_groups(size_t cnt, size_t group) { return (cnt + group - 1) / group; }
+void launch_rlc_sums(const uint32_t* H, const uint8_t* h_inf, const uint32_t* S, const uint8_t* s_inf,
+                     const uint8_t* cls, size_t cnt, uint64_t index0, const uint32_t* seed_words, size_t group,
+                     uint32_t* part, uint32_t* GH, uint8_t* g_hinf, uint32_t* GS, uint8_t* g_sinf, hipStream_t st);
+// exact fallback: the items of the failing groups fail[0 .. ) (ascending group indices) copied into m
+// compact slots (H / S layout of stride m, flags, class bytes), and their classes copied back
+void launch_rlc_gather(const uint32_t* fail, size_t group, size_t m, const uint32_t* H, const uint8_t* h_inf,
+                       const uint32_t* S, const uint8_t* s_inf, const uint8_t* cls, size_t cnt, uint32_t* CH,
+                       uint8_t* c_hinf, uint32_t* CS, uint8_t* c_sinf, uint8_t* ccls, hipStream_t st);
+void launch_rlc_scatter(const uint32_t* fail, size_t group, size_t m, const uint8_t* ccls, uint8_t* cls, size_t cnt,
+                        hipStream_t st);
+// test hook: ng staged points (stride ng) in the 96-byte compressed form
+void launch_rlc_compress(const uint32_t* GP, const uint8_t* g_inf, size_t ng, uint8_t* out96, hipStream_t st);
+
 // ---- latency path (k_lat.hip): one workgroup per item, the whole verification; writes cls[i] (REJ_*)
 int lat_trace_read(uint64_t* out, int n, hipStream_t st);  // phase marks of item 0 (wteam.h WV_MARK)
 int lat_trace_clear(hipStream_t st);

@@ -287,8 +287,74 @@ class Engine:
         self._check(self.lib.blsv_generate_chained_dev(self._h, _lib.buf(sk32), first_round, seg_len, d_seeds,
                                                        seed0_len, d_sigs, n, stream))
 
+    # ------------------------------------------------------------------ randomized batch verification
+    # Opt-in (include/blsverify.h soundness contract): one pairing check per group of G beacons with
+    # random 64-bit weights, the exact stages on every failing group. Same arguments and results as
+    # the exact methods; a call with n <= lat_max or n < 2 G is served by the exact entry point.
+    def verify_chained_rlc(self, first_round, prev0, sigs):
+        n = len(sigs)
+        if any(len(s) != 96 for s in sigs):
+            raise ValueError("chained signatures must be 96 bytes (reject wrong lengths host-side)")
+        sigb = b"".join(bytes(s) for s in sigs)
+        bm = _lib.out_buf((n + 7) // 8)
+        fb = ctypes.c_uint64()
+        cls = _lib.out_buf(n)
+        self._check(self.lib.blsv_verify_chained_rlc(self._h, first_round, _lib.buf(prev0), len(prev0), _lib.buf(sigb),
+                                                     n, bm, ctypes.byref(fb), cls))
+        return BatchResult(_bits(bm, n), None if fb.value == 2 ** 64 - 1 else fb.value, list(cls)[:n])
+
+    def verify_unchained_rlc(self, sigs, first_round=None, rounds=None):
+        n = len(sigs)
+        if any(len(s) != 96 for s in sigs):
+            raise ValueError("signatures must be 96 bytes (reject wrong lengths host-side)")
+        sigb = b"".join(bytes(s) for s in sigs)
+        rr = None
+        if rounds is not None:
+            rr = (ctypes.c_uint64 * max(n, 1))(*rounds)
+        bm = _lib.out_buf((n + 7) // 8)
+        fb = ctypes.c_uint64()
+        cls = _lib.out_buf(n)
+        self._check(self.lib.blsv_verify_unchained_rlc(self._h, rr, first_round or 0, _lib.buf(sigb), n, bm,
+                                                       ctypes.byref(fb), cls))
+        return BatchResult(_bits(bm, n), None if fb.value == 2 ** 64 - 1 else fb.value, list(cls)[:n])
+
+    def verify_chained_rlc_dev(self, first_round, seg_len, d_seeds, seed0_len, d_sigs, n, d_bitmap, d_first_bad,
+                               d_cls=None, stream=None, seg_phase=0):
+        """As verify_chained_dev, but synchronises the stream once per pass (blsv_verify_chained_rlc_dev)."""
+        self._check(self.lib.blsv_verify_chained_rlc_dev(self._h, first_round, seg_len, seg_phase, d_seeds, seed0_len,
+                                                         d_sigs, n, d_bitmap, d_first_bad, d_cls, stream))
+
+    def set_rlc_group(self, g):
+        """Group size of the randomized path (a power of two in [8, 4096], default 64); returns the
+        previous value."""
+        return self.lib.blsv_set_rlc_group(self._h, int(g))
+
+    def rlc_stats(self):
+        """(group checks, failed group checks, items re-run exactly) since the context was created."""
+        a, b, c = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(self.lib.blsv_rlc_stats(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+        return a.value, b.value, c.value
+
+    def test_rlc_seed(self, seed32):
+        """Pin the randomized path's seed (32 bytes; None = a fresh seed per call again)."""
+        if seed32 is not None and len(seed32) != 32:
+            raise ValueError("the seed is 32 bytes")
+        self._check(self.lib.blsv_test_rlc_seed(self._h, _lib.buf(seed32) if seed32 is not None else None))
+
+    def test_rlc_sums(self, first_round, prev0, sigs):
+        """blsv_test_rlc_sums: ([A_g], [B_g]) compressed, one pair per group of the chained range."""
+        n = len(sigs)
+        sigb = b"".join(bytes(s) for s in sigs)
+        cap = -(-n // 8) + n // 16384 + 1  # the smallest group, one short group per pass of the smallest chunk
+        a, b = _lib.out_buf(cap * 96), _lib.out_buf(cap * 96)
+        ng = self.lib.blsv_test_rlc_sums(self._h, first_round, _lib.buf(prev0), len(prev0), _lib.buf(sigb), n, a, b)
+        if ng < 0:
+            raise EngineError(ng, self.lib.blsv_last_error(self._h).decode())
+        ab, bb = bytes(a), bytes(b)
+        return ([ab[96 * k:96 * k + 96] for k in range(ng)], [bb[96 * k:96 * k + 96] for k in range(ng)])
+
     # ------------------------------------------------------------------ stage profiling
-    STAGES = ("hash", "decompress", "miller", "final_exp", "finish", "lat")
+    STAGES = ("hash", "decompress", "miller", "final_exp", "finish", "lat", "rlc")
 
     def profile(self, on=True):
         self._check(self.lib.blsv_profile_enable(self._h, 1 if on else 0))

@@ -284,6 +284,61 @@ size_t blsv_set_chunk(blsv_ctx* ctx, size_t items);
 /* HBM bytes of pipeline staging the context holds now (0 before its first batch). */
 size_t blsv_workspace_bytes(const blsv_ctx* ctx);
 
+/* ---------------------------------------------------------------- randomized batch verification
+ *
+ * Opt-in. The entry points above make the check chain.VerifyBeacon makes, once per beacon, and stay
+ * the default and the source of every headline number. The *_rlc entry points below take the argument
+ * lists and fill the outputs of their exact counterparts, but share one pairing check among each group
+ * of G consecutive beacons of a call (all under the group key set with blsv_set_group):
+ *
+ *   prod_i [ e(pk, H_i) e(-g1, sigma_i) ]^{r_i} = e(pk, sum r_i H_i) e(-g1, sum r_i sigma_i)
+ *
+ * with 64-bit weights r_i = the first 8 bytes, big-endian, of SHA-256(seed || BE64(i)), i the item's
+ * index within the call. The 32-byte seed is drawn from the OS CSPRNG (getrandom) once per call, after
+ * the inputs are fixed, is never reused and never returned; if the draw fails the call returns
+ * BLSV_EHIP. Decoding and the subgroup check stay exact and per item, and only items that decode
+ * (class 0 after that stage) enter a group's sums. The items of every group whose check fails are then
+ * run through the exact pairing stages.
+ *
+ * Soundness contract
+ *  - A reject is always the exact pipeline's reject: bitmap, first_bad and reject classes of a call
+ *    equal the exact entry point's whenever every invalid item is caught, and a valid item is never
+ *    rejected.
+ *  - An invalid item is accepted only if its group's check passes, which happens with probability at
+ *    most 2^-64 over the seed. The bound rests on every sigma_i lying in the order-r subgroup, which
+ *    the decompression stage has already checked.
+ *  - Cost: an all-valid call pays the combination stage plus n / G pairing checks. An adversary who
+ *    puts one bad round into every group forces the exact cost plus the combination stage.
+ *
+ * Routing: a call takes this path when n > lat_max and n >= 2 G; any other call is served by the exact
+ * entry point (and blsv_rlc_stats does not move). Not offered for blsv_verify_chained_multi,
+ * blsv_verify_prevs, message batches, the service or the latency path.
+ */
+int blsv_verify_chained_rlc(blsv_ctx* ctx, uint64_t first_round, const uint8_t* prev0, size_t prev0_len,
+                            const uint8_t* sigs96, size_t n, uint8_t* ok_bitmap, uint64_t* first_bad,
+                            uint8_t* reject_class);
+int blsv_verify_unchained_rlc(blsv_ctx* ctx, const uint64_t* rounds, uint64_t first_round, const uint8_t* sigs96,
+                              size_t n, uint8_t* ok_bitmap, uint64_t* first_bad, uint8_t* reject_class);
+/*
+ * As blsv_verify_chained_dev, with one difference: the call SYNCHRONISES `stream` once per pass (the
+ * group verdicts are read back to choose the items of the exact fallback), so it is not asynchronous;
+ * the outputs of the last pass are still only ordered on `stream`.
+ */
+int blsv_verify_chained_rlc_dev(blsv_ctx* ctx, uint64_t first_round, uint64_t seg_len, uint64_t seg_phase,
+                                const uint8_t* d_seeds96, size_t seed0_len, const uint8_t* d_sigs96, size_t n,
+                                uint64_t* d_bitmap, uint64_t* d_first_bad, uint8_t* d_reject_class, void* stream);
+/*
+ * Group size G of the randomized path: g rounded down to a power of two and clamped to [8, 4096].
+ * Default 64, chosen by measurement (profiles/rlc_bench.json). Returns the previous value.
+ */
+size_t blsv_set_rlc_group(blsv_ctx* ctx, size_t g);
+/*
+ * Counters of the randomized path since the context's creation: group checks made, group checks that
+ * failed, items re-run through the exact pairing stages (every item of a failing group). Any pointer
+ * may be NULL.
+ */
+int blsv_rlc_stats(blsv_ctx* ctx, uint64_t* groups, uint64_t* groups_failed, uint64_t* items_exact);
+
 /* ---------------------------------------------------------------- thread-safe service
  *
  * Concurrent single-item callers: the reference verifies each arrival in its own goroutine -- one per

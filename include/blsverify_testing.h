@@ -80,10 +80,11 @@ int blsv_test_service_limits(blsv_service* svc, size_t chunk, size_t lat_max, si
 
 /*
  * Stage timing for bench.py's roofline: when enabled, every stage launch (0 hash, 1 decompress,
- * 2 miller, 3 final_exp, 4 finish, 5 lat = a whole batch on the latency path) is bracketed by HIP
+ * 2 miller, 3 final_exp, 4 finish, 5 lat = a whole batch on the latency path, 6 rlc = the randomized
+ * path's combination stage with its gather and scatter) is bracketed by HIP
  * events on its launch stream. blsv_profile_read waits for the recorded events, writes per-stage
  * summed milliseconds, launch counts and items processed (arrays of nstages), clears the records and
- * returns the number of stages the engine defines (6).
+ * returns the number of stages the engine defines (7).
  */
 int blsv_profile_enable(blsv_ctx* ctx, int on);
 /*
@@ -109,6 +110,19 @@ int blsv_profile_read(blsv_ctx* ctx, double* ms, uint64_t* launches, uint64_t* i
  * BLSV_EINVAL for repeated indices.
  */
 int blsv_test_lagrange(const uint32_t* idx, size_t t, uint32_t* out);
+
+/*
+ * Randomized batch verification (blsverify.h blsv_verify_*_rlc). blsv_test_rlc_seed pins the 32-byte
+ * seed of every later call on this context (NULL returns to a fresh seed per call).
+ * blsv_test_rlc_sums runs the head (hash-to-G2, decompression, subgroup check) and the combination
+ * stage of a chained range with the context's group size, whatever n (no routing), and returns every
+ * group's two sums A_g = sum r_i H_i and B_g = sum r_i sigma_i in the 96-byte compressed form (infinity
+ * as 0xc0 || 0...). Returns the number of groups written to out_a96 / out_b96 each (ceil(cnt / G) per
+ * pass of cnt items, so at most ceil(n / 8) + n / 16384 + 1), or an error code < 0.
+ */
+int blsv_test_rlc_seed(blsv_ctx* ctx, const uint8_t* seed32);
+int blsv_test_rlc_sums(blsv_ctx* ctx, uint64_t first_round, const uint8_t* prev0, size_t prev0_len,
+                       const uint8_t* sigs96, size_t n, uint8_t* out_a96, uint8_t* out_b96);
 
 #ifdef __cplusplus
 }

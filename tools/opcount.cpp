@@ -6,12 +6,14 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <algorithm>
 #include <vector>
 
 #include "../drand_amd/csrc/pairing.h"
 #include "../drand_amd/csrc/hash.h"
 #include "../drand_amd/csrc/tri.h"
 #include "../drand_amd/csrc/testops.h"
+#include "../drand_amd/csrc/rlc.h"
 
 namespace bls {
 unsigned long long g_fp_mul_count = 0;
@@ -488,7 +490,83 @@ static int cmd_ops(bool list) {
   return 0;
 }
 
+// rlc <seed32hex> <G>: the randomized batch verification's combination stage (drand_amd/csrc/rlc.h) as
+// the device runs it -- lanes of RLC_LANE_ITEMS consecutive items, a group's lanes summed, to affine --
+// on the (message, signature) pairs read from stdin, one "msghex sighex" per line, item i = line i. A
+// message is hashed as KyberG2.Hash does, a signature decoded with the subgroup check; a decode reject
+// enters neither sum, a point at infinity not its own. Prints every group's sums A = sum r_i H_i and
+// B = sum r_i sigma_i compressed, and the Fp products of the stage per item, every predicated
+// addition counted as executed (the select form runs it whatever the bit).
+static int cmd_rlc(const char* seedhex, unsigned long G) {
+  const auto sb = unhex(seedhex);
+  if (sb.size() != 32 || G < (unsigned long)RLC_LANE_ITEMS || (G & (G - 1))) {
+    fprintf(stderr, "rlc: a 32-byte seed and a power-of-two group size >= %d\n", RLC_LANE_ITEMS);
+    return 2;
+  }
+  uint32_t seed[8];
+  for (int k = 0; k < 8; k++) seed[k] = load_be32(sb.data() + 4 * k);
+  std::vector<g2a> P[2];
+  std::vector<uint64_t> r[2];
+  static char line[8192];
+  while (fgets(line, sizeof line, stdin)) {
+    char* save = nullptr;
+    const char* mh = strtok_r(line, " \n", &save);
+    const char* sh = mh ? strtok_r(nullptr, " \n", &save) : nullptr;
+    if (!mh) continue;
+    if (!sh) return 2;
+    const auto msg = unhex(strcmp(mh, "-") ? mh : ""), sig = unhex(sh);
+    if (sig.size() != 96) return 2;
+    uint32_t b0[8];
+    xmd_b0_bytes(b0, msg.data(), (uint32_t)msg.size(), DST);
+    fp2 u0, u1;
+    xmd_tail_to_field(b0, u0, u1);
+    const g2j hj = hash_field_to_g2(u0, u1);
+    const bool hinf = jac_is_inf(hj);
+    g2a s;
+    bool sinf;
+    const uint8_t cls = g2_decompress(sig.data(), s, sinf, true);
+    const uint64_t ri = rlc_scalar(seed, P[0].size());
+    P[0].push_back(hinf ? g2a{fp2_zero(), fp2_zero()} : g2_to_aff(hj));
+    P[1].push_back(s);
+    r[0].push_back(cls == REJ_OK && !hinf ? ri : 0);
+    r[1].push_back(cls == REJ_OK && !sinf ? ri : 0);
+  }
+  const size_t n = P[0].size(), ng = (n + G - 1) / G, L = RLC_LANE_ITEMS;
+  if (!n) return 2;
+  const unsigned long long c0 = g_fp_mul_count;
+  std::vector<g2j> sums[2];
+  for (int w = 0; w < 2; w++) {
+    for (size_t g = 0; g < ng; g++) {
+      const size_t lo = g * G, hi = std::min(n, lo + G);
+      std::vector<g2j> part;
+      for (size_t i0 = lo; i0 < hi; i0 += L)
+        part.push_back(rlc_accumulate(
+            (int)std::min(L, hi - i0), [&](int k) { return P[w][i0 + k].x; }, [&](int k) { return P[w][i0 + k].y; },
+            [&](int k, int b) { return ((r[w][i0 + k] >> b) & 1u) != 0; }));
+      g2j sum = rlc_sum(part.size(), [&](size_t q) { return part[q]; });
+      if (!jac_is_inf(sum)) sum = jac_from_aff(g2_to_aff(sum));  // the device stores the affine form
+      sums[w].push_back(sum);
+    }
+  }
+  const unsigned long long total = g_fp_mul_count - c0;
+  printf("{\"items\": %zu, \"group\": %lu, \"groups\": %zu, ", n, G, ng);
+  for (int w = 0; w < 2; w++) {
+    printf("\"%s\": [", w ? "b" : "a");
+    for (size_t g = 0; g < ng; g++) {
+      uint8_t out[96];
+      g2_compress(out, sums[w][g]);
+      printf("%s\"", g ? ", " : "");
+      for (int k = 0; k < 96; k++) printf("%02x", out[k]);
+      printf("\"");
+    }
+    printf("], ");
+  }
+  printf("\"fp_mul\": %llu, \"fp_mul_per_item\": %.1f}\n", total, (double)total / (double)n);
+  return 0;
+}
+
 int main(int argc, char** argv) {
+  if (argc == 4 && !strcmp(argv[1], "rlc")) return cmd_rlc(argv[2], strtoul(argv[3], nullptr, 10));
   if (argc >= 2 && !strcmp(argv[1], "ops")) return cmd_ops(argc == 3 && !strcmp(argv[2], "list"));
   if (argc == 3 && !strcmp(argv[1], "hash")) return cmd_hash(argv[2]);
   if (argc == 3 && !strcmp(argv[1], "powfuzz")) return cmd_powfuzz(strtoul(argv[2], nullptr, 10));
