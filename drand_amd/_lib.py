@@ -107,6 +107,9 @@ SIGNATURES = {
     "blsv_rlc_stats": (ctypes.c_int, [vp, u64p, u64p, u64p]),
     "blsv_test_rlc_seed": (ctypes.c_int, [vp, u8p]),
     "blsv_test_rlc_sums": (ctypes.c_int, [vp, ctypes.c_uint64, u8p, sz, u8p, sz, u8p, u8p]),
+    "blsv_tlock_open": (ctypes.c_int, [vp, u8p, u8p, sz, u8p, u8p, u8p, u8p]),
+    "blsv_tlock_open_dev": (ctypes.c_int, [vp, u8p, vp, sz, vp, vp, vp]),
+    "blsv_tlock_stats": (ctypes.c_int, [vp, u64p, u64p]),
 }
 
 _lib = None

@@ -282,6 +282,61 @@ def verify_beacons(engine, public_key: bytes, beacons) -> list:
 
 
 # --------------------------------------------------------------------------------------------------
+# Timelock opening (core/timelock_test.go:43-60): the round's SignatureV2 is the IBE private key of
+# everything encrypted to that round; timelock.Decrypt pairs each ciphertext's U with it, derives a key
+# stream from the Gt value and XORs. Here all the ciphertexts of a round open in ONE engine call.
+
+def kdf_sha256_ctr(gt: bytes, n: int) -> bytes:
+    """This project's own example key-derivation: SHA-256(gt || BE32(counter)) blocks for counter =
+    0, 1, ..., truncated to n bytes. It is NOT kyber's: the reference derives its key stream with
+    BLAKE2Xs over ``GT.MarshalBinary``, which nothing in this repository can pin, so that KDF is not
+    restated here. A deployment that must open the reference's ciphertexts passes its own ``kdf``."""
+    out = b""
+    counter = 0
+    while len(out) < n:
+        out += hashlib.sha256(bytes(gt) + counter.to_bytes(4, "big")).digest()
+        counter += 1
+    return out[:n]
+
+
+def timelock_open(engine, round_: int, sig_v2: bytes, ciphertexts, kdf: Callable[[bytes, int], bytes],
+                  verify: bool = True) -> list:
+    """Opens every ciphertext locked to ``round_`` with that round's SignatureV2: ``ciphertexts`` is a
+    sequence of ``(U48, C)`` (the ephemeral point rP, compressed, and the masked message); returns
+    ``C XOR kdf(gt_i, len(C))`` per ciphertext with ``gt_i`` the 576-byte encoding of e(U_i, sig)^3
+    (``Engine.tlock_open``), or ``None`` where U did not decode.
+
+    ``verify=True`` first checks ``chain.VerifyBeaconV2`` of (round_, sig_v2) under the engine's group
+    key (``verify_unchained``) and raises ``VerifyError`` on a reject: a wrong "private key" otherwise
+    decrypts to silent garbage (the XXX of the reference's test). ``kdf(gt, n) -> n bytes`` is the
+    caller's (see ``kdf_sha256_ctr``)."""
+    sig_v2 = bytes(sig_v2)
+    if verify:
+        if len(sig_v2) != SIG_LEN:
+            raise VerifyError(round_, "bad length")
+        res = engine.verify_unchained([sig_v2], first_round=round_)
+        if not res.ok[0]:
+            from ._lib import REJ_NAMES
+            raise VerifyError(round_, REJ_NAMES.get(res.reject_class[0], "bls: invalid signature"))
+    cts = [(bytes(u), bytes(c)) for u, c in ciphertexts]
+    good = [k for k, (u, _) in enumerate(cts) if len(u) == 48]  # a wrong length is rejected host-side
+    res = engine.tlock_open(sig_v2, [cts[k][0] for k in good])
+    gts = [None] * len(cts)
+    for k, gt in zip(good, res.gt):
+        gts[k] = gt
+    out = []
+    for (_, c), gt in zip(cts, gts):
+        if gt is None:
+            out.append(None)
+            continue
+        ks = kdf(gt, len(c))
+        if len(ks) != len(c):
+            raise ValueError("kdf returned %d bytes for a %d-byte ciphertext" % (len(ks), len(c)))
+        out.append(bytes(a ^ b for a, b in zip(c, ks)))
+    return out
+
+
+# --------------------------------------------------------------------------------------------------
 # Threshold aggregation (SURVEY.md §8a row a17): chainStore.runAggregator (chain/beacon/chain.go:91-190)
 # and its partialCache / roundCache (chain/beacon/cache.go:18-182), restated. The cache, the gate and
 # the flush rules are host bookkeeping, as in the reference; the aggregation step itself (verify every

@@ -36,6 +36,14 @@ constexpr size_t kStagingBytesPerItem =
 static_assert(576ull * kMaxChunk < 0x7fffffffull, "SoA object resource exceeds its 31-bit num_records");
 static_assert((133ull * kMaxChunk) * 4 < 0xffffffffull, "SoA VGPR byte offset exceeds 32 bits");
 static_assert(48ull * 4 * kMaxChunk < 0x7fffffffull, "3-lane park slot resource exceeds 31 bits");  // park_n < 3.05 n
+// Timelock opening (blsv_tlock_open*, k_tlock.hip) runs in the pipeline staging as it is: the decoded
+// U table (G1_WORDS per item, AoS) with its flags and classes in H / h_inf / s_inf, f in F, the captured
+// final-exponentiation values in HQ (SoA, read by k_tlock_encode through one 12-slot object resource,
+// covered by the 576-byte assert above), and the encoded bytes of a host call back in F.
+static_assert(blsk::G1_WORDS <= blsk::H_WORDS, "timelock: the U table does not fit the H staging");
+static_assert(blsk::F_WORDS <= blsk::HQ_WORDS, "timelock: the captured Fp12 does not fit the HQ staging");
+static_assert(BLSV_GT_LEN == 4 * blsk::F_WORDS, "timelock: the Gt encoding is one F staging row per item");
+static_assert(BLSV_U_LEN <= 4 * blsk::S_WORDS, "timelock: a host call's compressed U bytes do not fit the S staging");
 
 struct DBuf {
   void* p = nullptr;
@@ -103,7 +111,8 @@ enum Stage {
   ST_FINISH = 4,
   ST_LAT = 5,
   ST_RLC = 6,
-  ST_N = 7
+  ST_TLOCK = 7,  // timelock opening: sigma's preparation and the f pass (its final exponentiation is ST_FEXP)
+  ST_N = 8
 };
 struct ProfRec {
   int stage;
@@ -167,6 +176,17 @@ struct rlc_state {
   PinBuf host;  // group verdicts down, failing group indices up
 };
 
+// Timelock opening (blsv_tlock_open*): the prepared form of the LAST sigma -- its 96 bytes, decode
+// class and flag, and the device table of its 68 lines' P-independent coefficients. One entry: a call
+// with another sigma replaces it.
+struct tlock_state {
+  bool valid = false;
+  uint8_t sig[96] = {0};
+  uint8_t cls = 0;
+  uint64_t prepared = 0, items = 0;  // blsv_tlock_stats
+  DBuf d_sig, S, s_inf, s_cls, tab;
+};
+
 struct blsv_ctx {
   int device = 0;
   bool prof = false;
@@ -225,6 +245,7 @@ struct blsv_ctx {
   // randomized batch verification (blsv_verify_*_rlc, rlc.h): the lanes' partial sums, one H / S slot per
   // group with flags and class bytes, the compact staging of the exact fallback, the failing groups
   rlc_state rlc;
+  tlock_state tlock;
 };
 
 #define HIPCHK(ctx, expr)                                                             \

@@ -88,6 +88,19 @@ void launch_rlc_scatter(const uint32_t* fail, size_t group, size_t m, const uint
 // test hook: ng staged points (stride ng) in the 96-byte compressed form
 void launch_rlc_compress(const uint32_t* GP, const uint8_t* g_inf, size_t ng, uint8_t* out96, hipStream_t st);
 
+// ---- timelock opening (k_tlock.hip, tlock.h): E_i = e(U_i, sigma)^3 under one shared sigma.
+// prepare: sigma's decoded one-entry staging (launch_decompress_g2 with cnt = 1: S of stride 1, flag,
+// class) -> tab, kTlockTabWords words of P-independent line coefficients (untouched when sigma did not
+// decode or is the point at infinity). f: U / u_inf / cls as launch_decompress_g1 wrote them for cnt
+// items, sig_inf = sigma's device flag -> F (SoA of stride cnt; 1 for a pair with a point at infinity,
+// untouched for cls != 0). encode: the captured values E (SoA of stride cnt) -> cnt x 576 bytes (out
+// 4-byte aligned), zeros where cls != 0.
+constexpr size_t kTlockTabWords = 68 * 3 * 24;
+void launch_tlock_prepare(const uint32_t* S, const uint8_t* s_inf, const uint8_t* s_cls, uint32_t* tab, hipStream_t st);
+void launch_tlock_f(const uint32_t* tab, const uint32_t* U, const uint8_t* u_inf, const uint8_t* cls,
+                    const uint8_t* sig_inf, size_t cnt, uint32_t* F, hipStream_t st);
+void launch_tlock_encode(const uint32_t* E, const uint8_t* cls, size_t cnt, uint8_t* out, hipStream_t st);
+
 // ---- latency path (k_lat.hip): one workgroup per item, the whole verification; writes cls[i] (REJ_*)
 int lat_trace_read(uint64_t* out, int n, hipStream_t st);  // phase marks of item 0 (wteam.h WV_MARK)
 int lat_trace_clear(hipStream_t st);

@@ -37,6 +37,23 @@ class BatchResult:
         return bytes(out)
 
 
+class SignatureRejected(EngineError):
+    """The shared signature of a timelock opening did not decode (sig_class = REJ_* 2-6)."""
+
+    def __init__(self, code, msg, sig_class):
+        super().__init__(code, msg)
+        self.sig_class = sig_class
+
+
+@dataclass
+class TlockResult:
+    """Outcome of Engine.tlock_open: ok[i] (U_i decoded), reject classes (REJ_*), gt[i] = the 576-byte
+    encoding of e(U_i, sigma)^3 or None for a rejected U."""
+    ok: list
+    reject_class: list
+    gt: list
+
+
 def _bits(bitmap, n):
     import numpy as np
     if n == 0:
@@ -353,8 +370,51 @@ class Engine:
         ab, bb = bytes(a), bytes(b)
         return ([ab[96 * k:96 * k + 96] for k in range(ng)], [bb[96 * k:96 * k + 96] for k in range(ng)])
 
+    # ------------------------------------------------------------------ timelock opening
+    # include/blsverify.h "timelock": E_i = e(U_i, sigma)^3 for one shared round signature, 576 bytes
+    # each (coefficient order and exponent as the header states them; parity with kilic unpinned).
+    def tlock_open(self, sig, us):
+        """blsv_tlock_open: TlockResult(ok, reject_class, gt) over the compressed G1 points `us` under
+        the 96-byte round signature `sig`; gt[i] is 576 bytes, or None where U_i did not decode.
+        Raises SignatureRejected (an EngineError, .sig_class = REJ_*) when sig does not decode. The
+        signature is NOT verified here."""
+        sig = bytes(sig)
+        us = [bytes(u) for u in us]
+        if len(sig) != 96:
+            raise ValueError("the round signature is 96 bytes")
+        if any(len(u) != 48 for u in us):
+            raise ValueError("U values must be 48 bytes (reject wrong lengths host-side)")
+        n = len(us)
+        out = _lib.out_buf(n * 576)
+        ok = _lib.out_buf(n)
+        cls = _lib.out_buf(n)
+        sc = ctypes.c_uint8()
+        rc = self.lib.blsv_tlock_open(self._h, _lib.buf(sig), _lib.buf(b"".join(us)), n, out, ok, cls,
+                                      ctypes.cast(ctypes.byref(sc), u8p))
+        if rc == _lib.BLSV_EINVAL and sc.value:
+            raise SignatureRejected(rc, self.lib.blsv_last_error(self._h).decode(), sc.value)
+        self._check(rc)
+        ob = bytes(out)
+        oks = [bool(x) for x in list(ok)[:n]]
+        return TlockResult(oks, list(cls)[:n], [ob[576 * i:576 * i + 576] if oks[i] else None for i in range(n)])
+
+    def tlock_open_dev(self, sig, d_us, n, d_out, d_cls=None, stream=None):
+        """blsv_tlock_open_dev: n device-resident U values (48 bytes each) -> n x 576 bytes at d_out
+        (4-byte aligned), optional class bytes at d_cls; asynchronous on `stream` except for the
+        read-back of a new signature's decode class."""
+        sig = bytes(sig)
+        if len(sig) != 96:
+            raise ValueError("the round signature is 96 bytes")
+        self._check(self.lib.blsv_tlock_open_dev(self._h, _lib.buf(sig), d_us, n, d_out, d_cls, stream))
+
+    def tlock_stats(self):
+        """(signatures prepared, U values processed) since the context was created."""
+        a, b = ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(self.lib.blsv_tlock_stats(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
+
     # ------------------------------------------------------------------ stage profiling
-    STAGES = ("hash", "decompress", "miller", "final_exp", "finish", "lat", "rlc")
+    STAGES = ("hash", "decompress", "miller", "final_exp", "finish", "lat", "rlc", "tlock")
 
     def profile(self, on=True):
         self._check(self.lib.blsv_profile_enable(self._h, 1 if on else 0))

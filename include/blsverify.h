@@ -339,6 +339,67 @@ size_t blsv_set_rlc_group(blsv_ctx* ctx, size_t g);
  */
 int blsv_rlc_stats(blsv_ctx* ctx, uint64_t* groups, uint64_t* groups_failed, uint64_t* items_exact);
 
+/* ---------------------------------------------------------------- timelock
+ *
+ * What SignatureV2 exists for (core/timelock_test.go:43-60): a message is encrypted to a future round
+ * under the group key, and that round's SignatureV2 is the IBE private key that opens it --
+ * timelock.Decrypt(key.Pairing, private, ciphertext) pairs the ciphertext's ephemeral point U = rP
+ * with the signature. When a round arrives everything locked to it opens at once: n pairings
+ * e(U_i, sigma) with ONE shared G2 argument. blsv_tlock_open computes them in one call.
+ *
+ * Inputs
+ *  - sig96: the round's compressed G2 signature, decoded as every signature is (kilic
+ *    G2.FromCompressed with the subgroup check). A sigma that does not decode makes the call return
+ *    BLSV_EINVAL with its BLSV_REJ_* class (2-6) in *sig_class; the per-item outputs are left untouched
+ *    (the precedent of a key that does not decode). *sig_class = 0 otherwise. The call does NOT check
+ *    that sigma is the round's signature: verify it first (blsv_verify_unchained), a wrong "private
+ *    key" opens to garbage without any error.
+ *  - us48: n compressed G1 points (BLSV_U_LEN bytes each), decoded per item by the rules of a public
+ *    key (kilic G1.FromCompressed, subgroup check included). An item whose U does not decode gets
+ *    ok[i] = 0, reject_class[i] = BLSV_REJ_* 2-6 and BLSV_GT_LEN zero bytes; its neighbours are unaffected.
+ *
+ * Output: out_gt576[i] = E_i = e(U_i, sigma)^3 with e the reduced pairing f^((p^12 - 1)/r), i.e. the
+ * Miller value raised to (p^6 - 1)(p^2 + 1) * lambda with lambda = 3 (p^4 - p^2 + 1)/r =
+ * (x-1)^2 (x+p) (x^2+p^2-1) + 3 -- the hard part every verification here runs, and the exponent of
+ * kilic's finalExp as recalled. A pair with U or sigma at infinity is skipped as kilic's engine skips
+ * it: E_i = 1, ok[i] = 1. ok[i] = 1 means "U decoded", nothing more.
+ *
+ * Encoding of E_i: twelve canonical Fp values (out of Montgomery form, fully reduced), 48 bytes
+ * big-endian each, highest tower coefficient first: c1.c2.c1, c1.c2.c0, c1.c1.c1, c1.c1.c0, c1.c0.c1,
+ * c1.c0.c0, c0.c2.c1, c0.c2.c0, c0.c1.c1, c0.c1.c0, c0.c0.c1, c0.c0.c0 (Fp12 = Fp6[w]/(w^2 - v),
+ * Fp6 = Fp2[v]/(v^3 - (1 + i)), x.cK.cJ.cI = coefficient of w^K v^J i^I). The encoding of 1 is 575 zero
+ * bytes and a final 0x01.
+ *
+ * PARITY UNPINNED, two items: the exponent lambda (the cube) and the coefficient order above are kilic
+ * GT marshalling as recalled; the reference holds no Gt fixture (its timelock test only round-trips
+ * random data), so neither is pinned against it. Both are pinned against this repository's own oracle.
+ * The KDF that turns E_i into a key stream is the caller's (kyber's is BLAKE2Xs over GT.MarshalBinary).
+ *
+ * Prepared-signature cache: the context keeps the prepared form of the LAST sigma (its 96 bytes and
+ * the table of its 68 Miller lines' P-independent coefficients, 19,584 bytes on the device). A call with
+ * the same 96 bytes prepares nothing; any other sigma replaces the entry (one entry: A, B, A prepares
+ * three times). blsv_tlock_stats: *prepared = preparations made (a sigma that does not decode is not
+ * counted), *items = U values processed (rejected ones included) since the context's creation; either
+ * pointer may be NULL.
+ *
+ * Sizing: the pipeline staging is used as it is (memory contract above, unchanged); more than a chunk
+ * of items runs in chunk-sized passes with identical outputs. One lane per item serves every n: there
+ * is no latency-path form and no service entry.
+ *
+ * blsv_tlock_open_dev: d_us48 / d_out_gt576 (4-byte aligned) / d_reject_class (optional; 0 = opened)
+ * are device pointers, sig96 is host memory. Sigma's decode class is read back (one 1-byte copy and
+ * one synchronisation of `stream`) only when the signature is not the cached one; everything else is
+ * asynchronous on `stream` under the single-stream rule of blsv_verify_chained_dev. Returns
+ * BLSV_EINVAL for a sigma that does not decode (class in blsv_last_error's text).
+ */
+#define BLSV_U_LEN 48
+#define BLSV_GT_LEN 576
+int blsv_tlock_open(blsv_ctx* ctx, const uint8_t* sig96, const uint8_t* us48, size_t n, uint8_t* out_gt576,
+                    uint8_t* ok, uint8_t* reject_class, uint8_t* sig_class);
+int blsv_tlock_open_dev(blsv_ctx* ctx, const uint8_t* sig96, const uint8_t* d_us48, size_t n, uint8_t* d_out_gt576,
+                        uint8_t* d_reject_class, void* stream);
+int blsv_tlock_stats(blsv_ctx* ctx, uint64_t* prepared, uint64_t* items);
+
 /* ---------------------------------------------------------------- thread-safe service
  *
  * Concurrent single-item callers: the reference verifies each arrival in its own goroutine -- one per

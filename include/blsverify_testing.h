@@ -81,10 +81,11 @@ int blsv_test_service_limits(blsv_service* svc, size_t chunk, size_t lat_max, si
 /*
  * Stage timing for bench.py's roofline: when enabled, every stage launch (0 hash, 1 decompress,
  * 2 miller, 3 final_exp, 4 finish, 5 lat = a whole batch on the latency path, 6 rlc = the randomized
- * path's combination stage with its gather and scatter) is bracketed by HIP
+ * path's combination stage with its gather and scatter, 7 tlock = the timelock opening's preparation
+ * of sigma and its f pass; its U decode and final exponentiation count as 1 and 3) is bracketed by HIP
  * events on its launch stream. blsv_profile_read waits for the recorded events, writes per-stage
  * summed milliseconds, launch counts and items processed (arrays of nstages), clears the records and
- * returns the number of stages the engine defines (7).
+ * returns the number of stages the engine defines (8).
  */
 int blsv_profile_enable(blsv_ctx* ctx, int on);
 /*

@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
+#include <string>
 #include <vector>
 
 #include "../drand_amd/csrc/pairing.h"
@@ -14,6 +15,7 @@
 #include "../drand_amd/csrc/tri.h"
 #include "../drand_amd/csrc/testops.h"
 #include "../drand_amd/csrc/rlc.h"
+#include "../drand_amd/csrc/tlock.h"
 
 namespace bls {
 unsigned long long g_fp_mul_count = 0;
@@ -565,7 +567,94 @@ static int cmd_rlc(const char* seedhex, unsigned long G) {
   return 0;
 }
 
+// tlock <sig96hex>: the timelock opening (drand_amd/csrc/tlock.h) as the device runs it -- sigma
+// decoded with the subgroup check and prepared once into the table of P-independent line coefficients,
+// then per U (stdin, one 48-byte compressed G1 point in hex per line) the f pass against the table, the
+// final exponentiation and the 576-byte Gt encoding. A U that does not decode prints null and its
+// class; a pair with a point at infinity is skipped (E = 1). "lines_match": every table line times
+// (xU, yU) equals, as field elements, the line miller_lines (miller_dbl_step / miller_add_step) emits
+// for the same pair, and the f pass equals miller_loop_multi<1>. Prints the Fp products of the
+// preparation (once per sigma) and of one item's f pass and final exponentiation.
+static int cmd_tlock(const char* sighex) {
+  const auto sig = unhex(sighex);
+  if (sig.size() != 96) return 2;
+  g2a Q;
+  bool qinf;
+  const uint8_t scls = g2_decompress(sig.data(), Q, qinf, true);
+  if (scls != REJ_OK) {
+    printf("{\"sig_class\": %d}\n", scls);
+    return 1;
+  }
+  static fp2 tab[MILLER_STEPS][3];
+  unsigned long long n_prepare = 0, n_f = 0, n_fexp = 0;
+  if (!qinf) {
+    const unsigned long long c0 = g_fp_mul_count;
+    tlock_prepare(Q, [&](int step, int c, const fp2& v) { tab[step][c] = v; });
+    n_prepare = g_fp_mul_count - c0;
+  }
+  auto coef = [&](int step, int c) { return tab[step][c]; };
+  bool lines_match = true;
+  std::vector<std::string> enc;
+  std::vector<int> classes;
+  static char line_buf[256];
+  while (fgets(line_buf, sizeof line_buf, stdin)) {
+    char* save = nullptr;
+    const char* uh = strtok_r(line_buf, " \n", &save);
+    if (!uh) continue;
+    const auto ub = unhex(uh);
+    if (ub.size() != 48) return 2;
+    g1a U;
+    bool uinf;
+    const uint8_t cls = g1_decompress(ub.data(), U, uinf);
+    classes.push_back(cls);
+    if (cls != REJ_OK) {
+      enc.push_back("");
+      continue;
+    }
+    fp12 f = fp12_one();
+    if (!uinf && !qinf) {
+      unsigned long long c0 = g_fp_mul_count;
+      f = tlock_f(coef, U.x, U.y);
+      n_f = g_fp_mul_count - c0;
+      // the lines and the value of the two-pass Miller loop for the same pair
+      miller_lines(U, [&]() { return Q; }, [&](int step, const line& l) {
+        const line t = tlock_line(coef, step, U.x, U.y);
+        lines_match &= fp2_eq(t.a0, l.a0) && fp2_eq(t.a1, l.a1) && fp2_eq(t.a4, l.a4);
+      });
+      const g1a Ps[1] = {U};
+      const g2a Qs[1] = {Q};
+      const bool act[1] = {true};
+      lines_match &= fp12_eq(f, miller_loop_multi<1>(Ps, Qs, act));
+    }
+    const unsigned long long c1 = g_fp_mul_count;
+    const fp12 e = final_exponentiation(f);
+    n_fexp = g_fp_mul_count - c1;
+    uint8_t out[TLOCK_GT_LEN];
+    tlock_encode(out, e);
+    std::string h;
+    char b[3];
+    for (int k = 0; k < TLOCK_GT_LEN; k++) {
+      snprintf(b, sizeof b, "%02x", out[k]);
+      h += b;
+    }
+    enc.push_back(h);
+  }
+  printf("{\"sig_class\": 0, \"sig_inf\": %s, \"lines_match\": %s, \"class\": [", qinf ? "true" : "false",
+         lines_match ? "true" : "false");
+  for (size_t i = 0; i < classes.size(); i++) printf("%s%d", i ? ", " : "", classes[i]);
+  printf("], \"e\": [");
+  for (size_t i = 0; i < enc.size(); i++) {
+    if (enc[i].empty())
+      printf("%snull", i ? ", " : "");
+    else
+      printf("%s\"%s\"", i ? ", " : "", enc[i].c_str());
+  }
+  printf("], \"fp_mul\": {\"tlock_prepare\": %llu, \"tlock_f\": %llu, \"final_exp\": %llu}}\n", n_prepare, n_f, n_fexp);
+  return lines_match ? 0 : 1;
+}
+
 int main(int argc, char** argv) {
+  if (argc == 3 && !strcmp(argv[1], "tlock")) return cmd_tlock(argv[2]);
   if (argc == 4 && !strcmp(argv[1], "rlc")) return cmd_rlc(argv[2], strtoul(argv[3], nullptr, 10));
   if (argc >= 2 && !strcmp(argv[1], "ops")) return cmd_ops(argc == 3 && !strcmp(argv[2], "list"));
   if (argc == 3 && !strcmp(argv[1], "hash")) return cmd_hash(argv[2]);
@@ -575,8 +664,9 @@ int main(int argc, char** argv) {
   if (argc == 3 && !strcmp(argv[1], "linfuzz")) return cmd_linfuzz(strtoul(argv[2], nullptr, 10));
   if (argc == 3 && !strcmp(argv[1], "f6fuzz")) return cmd_f6fuzz(strtoul(argv[2], nullptr, 10));
   if (argc != 5) {
-    fprintf(stderr, "usage: %s pk48hex round prevhex|- sig96hex   (prev '-' = unchained V2)\n       %s hash msghex\n",
-            argv[0], argv[0]);
+    fprintf(stderr, "usage: %s pk48hex round prevhex|- sig96hex   (prev '-' = unchained V2)\n       %s hash msghex\n"
+            "       %s tlock sig96hex   (one compressed U in hex per line on stdin)\n",
+            argv[0], argv[0], argv[0]);
     return 2;
   }
   auto pk = unhex(argv[1]);
