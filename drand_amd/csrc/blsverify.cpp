@@ -344,14 +344,27 @@ static bool serial_stages() {
   return on;
 }
 
+// Stage 2 of run_head. fused_subgroup: the tail is run_tail, whose Miller lines pass closes the signatures' psi subgroup
+// check on its own [|x|]sigma (k_miller.hip), so the head only decodes. The explicit subgroup kernels
+// stay for run_tail_rlc (its combination stage sums signatures before any Miller loop, on the strength
+// of that check) and under blsv_test_generic_chains (the hook exists to exercise them).
+static void head_decompress(blsv_ctx* c, const uint8_t* d_sigs, size_t stride, size_t offset, size_t base, size_t cnt,
+                            bool fused_subgroup, hipStream_t st) {
+  if (fused_subgroup && !blsk::g_generic_chains_all)
+    blsk::launch_decompress_g2_only(d_sigs, stride, offset, base, cnt, c->S.as<uint32_t>(), c->s_inf.as<uint8_t>(),
+                                    c->cls.as<uint8_t>(), st);
+  else
+    blsk::launch_decompress_g2(d_sigs, stride, offset, base, cnt, c->S.as<uint32_t>(), c->s_inf.as<uint8_t>(),
+                               c->cls.as<uint8_t>(), st);
+}
+
 template <typename HashFn>
 static int run_head(blsv_ctx* c, const uint8_t* d_sigs, size_t stride, size_t offset, size_t base, size_t cnt,
-                    hipStream_t st, HashFn hash) {
+                    bool fused_subgroup, hipStream_t st, HashFn hash) {
   if (serial_stages()) {
     {
       StageTimer tm(c, ST_DECOMP, cnt, st);
-      blsk::launch_decompress_g2(d_sigs, stride, offset, base, cnt, c->S.as<uint32_t>(), c->s_inf.as<uint8_t>(),
-                                 c->cls.as<uint8_t>(), st);
+      head_decompress(c, d_sigs, stride, offset, base, cnt, fused_subgroup, st);
     }
     StageTimer tm(c, ST_HASH, cnt, st);
     hash();
@@ -361,8 +374,7 @@ static int run_head(blsv_ctx* c, const uint8_t* d_sigs, size_t stride, size_t of
   HIPCHK(c, hipStreamWaitEvent(c->side, c->fork_ev, 0));
   {
     StageTimer tm(c, ST_DECOMP, cnt, c->side);
-    blsk::launch_decompress_g2(d_sigs, stride, offset, base, cnt, c->S.as<uint32_t>(), c->s_inf.as<uint8_t>(),
-                               c->cls.as<uint8_t>(), c->side);
+    head_decompress(c, d_sigs, stride, offset, base, cnt, fused_subgroup, c->side);
   }
   HIPCHK(c, hipEventRecord(c->join_ev, c->side));
   {
@@ -373,7 +385,9 @@ static int run_head(blsv_ctx* c, const uint8_t* d_sigs, size_t stride, size_t of
   return BLSV_OK;
 }
 
-// Stages 3..5 (Miller, final exponentiation, finish) after run_head
+// Stages 3..5 (Miller, final exponentiation, finish) after run_head(fused_subgroup = true): the Miller
+// lines pass rejects the signatures outside G2 (REJ_NOT_IN_SUBGROUP; lanes the explicit kernels
+// already rejected return early)
 static int run_tail(blsv_ctx* c, const uint8_t* d_sigs, size_t stride, size_t offset, size_t base, size_t cnt,
                     const PkSel& pk, uint64_t* d_bitmap, unsigned long long* d_first_bad, uint8_t* d_cls_out,
                     hipStream_t st, uint64_t label0 = 0) {
@@ -384,7 +398,7 @@ static int run_tail(blsv_ctx* c, const uint8_t* d_sigs, size_t stride, size_t of
     StageTimer tm(c, ST_MILLER, cnt, st);
     blsk::launch_miller(pk.tab, pk.inf, pk.idx, c->H.as<uint32_t>(), c->h_inf.as<uint8_t>(), c->S.as<uint32_t>(),
                         c->s_inf.as<uint8_t>(), c->cls.as<uint8_t>(), cnt, c->F.as<uint32_t>(), c->LN.as<uint32_t>(),
-                        std::min(cnt, kLineSub), c->FW.as<uint32_t>(), st);
+                        std::min(cnt, kLineSub), c->FW.as<uint32_t>(), true, st);
   }
   {
     StageTimer tm(c, ST_FEXP, cnt, st);
@@ -474,7 +488,7 @@ static int verify_driver(blsv_ctx* c, size_t n, const uint8_t* d_sigs, size_t st
   if (reject_class) HIPCHK(c, c->misc.ensure(n + 64));
   for (size_t base = 0; base < n; base += c->cap) {
     const size_t cnt = std::min(c->cap, n - base);
-    rc = run_head(c, d_sigs, stride, offset, base, cnt, c->stream, [&]() { hash(base, cnt); });
+    rc = run_head(c, d_sigs, stride, offset, base, cnt, true, c->stream, [&]() { hash(base, cnt); });
     if (rc) return rc;
     rc = run_tail(c, d_sigs, stride, offset, base, cnt, pk, c->bitmap.as<uint64_t>(),
                   c->first_bad.as<unsigned long long>(), reject_class ? c->misc.as<uint8_t>() : nullptr, c->stream);
@@ -544,7 +558,7 @@ static void rlc_pairing_check(blsv_ctx* c, const uint32_t* H, const uint8_t* h_i
   {
     StageTimer tm(c, ST_MILLER, cnt, st);
     blsk::launch_miller(pk.tab, pk.inf, pk.idx, H, h_inf, S, s_inf, cls, cnt, c->F.as<uint32_t>(),
-                        c->LN.as<uint32_t>(), std::min(cnt, kLineSub), c->FW.as<uint32_t>(), st);
+                        c->LN.as<uint32_t>(), std::min(cnt, kLineSub), c->FW.as<uint32_t>(), false, st);
   }
   StageTimer tm(c, ST_FEXP, cnt, st);
   blsk::launch_final_exp(c->F.as<uint32_t>(), c->FW.as<uint32_t>(), cnt, cls, st, c->LN.as<uint32_t>());
@@ -623,7 +637,7 @@ static int verify_driver_rlc(blsv_ctx* c, size_t n, const uint8_t* d_sigs, HashF
   if (reject_class) HIPCHK(c, c->misc.ensure(n + 64));
   for (size_t base = 0; base < n; base += c->cap) {
     const size_t cnt = std::min(c->cap, n - base);
-    rc = run_head(c, d_sigs, 96, 0, base, cnt, c->stream, [&]() { hash(base, cnt); });
+    rc = run_head(c, d_sigs, 96, 0, base, cnt, false, c->stream, [&]() { hash(base, cnt); });
     if (rc) return rc;
     rc = run_tail_rlc(c, base, cnt, seed, c->bitmap.as<uint64_t>(), c->first_bad.as<unsigned long long>(),
                       reject_class ? c->misc.as<uint8_t>() : nullptr, c->stream);
@@ -714,7 +728,7 @@ int svc_verify_mixed(blsv_ctx* c, size_t n, const uint8_t* msgs, const uint64_t*
       // the Miller stage indexes pk_idx by the chunk-local item: hand it this pass's slice of the
       // per-item key entries (a batch spans several passes once an OOM halving shrank the chunk)
       const PkSel pk{d_tab, d_tab_inf, d_idx + base};
-      rc = run_head(c, d_sig, 96, 0, base, cnt, c->stream, [&]() {
+      rc = run_head(c, d_sig, 96, 0, base, cnt, true, c->stream, [&]() {
         blsk::launch_hash_messages(d_msg, d_off + base, d_len + base, cnt, c->H.as<uint32_t>(), c->h_inf.as<uint8_t>(),
                                    c->HQ.as<uint32_t>(), c->stream);
       });
@@ -1111,7 +1125,7 @@ static int partials_stage(blsv_ctx* c, const uint8_t* msg, size_t msg_len, const
     HIPCHK(c, hipMemsetAsync(c->first_bad.p, 0xff, 8, c->stream));
     blsk::launch_hash_messages(c->in_msgs.as<uint8_t>(), c->in_off.as<uint64_t>(), c->in_len.as<uint32_t>(), k,
                                c->H.as<uint32_t>(), c->h_inf.as<uint8_t>(), c->HQ.as<uint32_t>(), c->stream);
-    rc = run_head(c, c->in_sigs.as<uint8_t>(), partial_len, 2, 0, k, c->stream, []() {});  // hashed above
+    rc = run_head(c, c->in_sigs.as<uint8_t>(), partial_len, 2, 0, k, true, c->stream, []() {});  // hashed above
     if (rc) return rc;
     rc = run_tail(c, c->in_sigs.as<uint8_t>(), partial_len, 2, 0, k, pk, c->bitmap.as<uint64_t>(),
                   c->first_bad.as<unsigned long long>(), nullptr, c->stream);
@@ -1547,7 +1561,7 @@ int blsv_verify_chained_dev(blsv_ctx* c, uint64_t first_round, uint64_t seg_len,
   }
   for (size_t base = 0; base < n; base += c->cap) {
     const size_t cnt = std::min(c->cap, n - base);
-    rc = run_head(c, d_sigs96, 96, 0, base, cnt, st, [&]() {
+    rc = run_head(c, d_sigs96, 96, 0, base, cnt, true, st, [&]() {
       blsk::launch_hash_chained(src, base, cnt, c->H.as<uint32_t>(), c->h_inf.as<uint8_t>(), c->HQ.as<uint32_t>(), st);
     });
     if (rc) return rc;
@@ -1658,7 +1672,7 @@ int blsv_verify_chained_rlc_dev(blsv_ctx* c, uint64_t first_round, uint64_t seg_
   blsk::ChainedSrc src{d_sigs96, d_seeds96, first_round, seg_len ? seg_len : n, (uint32_t)seed0_len, seg_phase};
   for (size_t base = 0; base < n; base += c->cap) {
     const size_t cnt = std::min(c->cap, n - base);
-    rc = run_head(c, d_sigs96, 96, 0, base, cnt, st, [&]() {
+    rc = run_head(c, d_sigs96, 96, 0, base, cnt, false, st, [&]() {
       blsk::launch_hash_chained(src, base, cnt, c->H.as<uint32_t>(), c->h_inf.as<uint8_t>(), c->HQ.as<uint32_t>(), st);
     });
     if (rc) return rc;
@@ -1712,7 +1726,7 @@ int blsv_test_rlc_sums(blsv_ctx* c, uint64_t first_round, const uint8_t* prev0, 
   size_t done = 0;  // groups written so far
   for (size_t base = 0; base < n; base += c->cap) {
     const size_t cnt = std::min(c->cap, n - base), ng = blsk::rlc_groups(cnt, r.group);
-    rc = run_head(c, c->in_sigs.as<uint8_t>(), 96, 0, base, cnt, c->stream, [&]() {
+    rc = run_head(c, c->in_sigs.as<uint8_t>(), 96, 0, base, cnt, false, c->stream, [&]() {
       blsk::launch_hash_chained(src, base, cnt, c->H.as<uint32_t>(), c->h_inf.as<uint8_t>(), c->HQ.as<uint32_t>(),
                                 c->stream);
     });

@@ -1,5 +1,10 @@
 // Stage 2: signature decompression (ZCash format) + psi-based G2 subgroup check, and the final
 // verdict reduction (bitmap + first bad index). kilic G2.FromCompressed order [ext].
+// The subgroup kernels here serve the paths that need the verdict before any Miller loop: the
+// randomized batch verification (it sums signatures first), the timelock sigma, and the test hook
+// blsv_test_generic_chains. The per-item batch path launches the decoding alone
+// (launch_decompress_g2_only) and closes the check in its Miller lines pass, which walks the same
+// [|x|]sigma anyway (k_miller.hip, pairing.h miller_t_in_subgroup).
 // The in-place Fp2 products of this unit's G2 chains use the Karatsuba body (tower.h
 // fp2_mul_inl): their live state leaves room for its extra operand arrays here, unlike the Miller
 // lines kernel (same-box A/B, profiles/r05_ab.json r05l: hash + decompression 100.7 -> 98.6 ms).
@@ -129,12 +134,12 @@ void launch_decompress_g2(const uint8_t* sigs, size_t stride, size_t offset, siz
                      g_generic_chains_all);
 }
 
-// decoding only (no subgroup check): the speculative recovery's shares, whose validity the round's
-// own partial verification decides (blsverify.cpp spec_recover_launch)
-void launch_decompress_g2_only(const uint8_t* sigs, size_t stride, size_t offset, size_t cnt, uint32_t* S,
-                               uint8_t* s_inf, uint8_t* cls, hipStream_t st) {
+// decoding only: the head of the per-item batch path (blsverify.cpp run_head), whose Miller lines pass
+// closes the subgroup check on its own [|x|]sigma (k_miller.hip k_miller_lines<true>)
+void launch_decompress_g2_only(const uint8_t* sigs, size_t stride, size_t offset, size_t base, size_t cnt,
+                               uint32_t* S, uint8_t* s_inf, uint8_t* cls, hipStream_t st) {
   if (!cnt) return;
-  hipLaunchKernelGGL(k_decompress_g2, dim3(grid_for(cnt)), dim3(TPB), 0, st, sigs, stride, offset, size_t(0), cnt, S,
+  hipLaunchKernelGGL(k_decompress_g2, dim3(grid_for(cnt)), dim3(TPB), 0, st, sigs, stride, offset, base, cnt, S,
                      s_inf, cls);
 }
 

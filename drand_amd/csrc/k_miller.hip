@@ -4,7 +4,12 @@
 // own state live, which removes the scratch spills of the fused loop (13.6 KB/lane, ~160 KB of
 // scratch traffic per beacon) for 2 x 39 KB of coalesced line traffic per beacon, and lets the
 // lines pass run at 2 waves/SIMD (256 VGPRs).
+// The lines pass of the pair (-g1, sigma) ends with T = [|x|]sigma, which is what sigma's psi subgroup
+// check needs: k_miller_lines<true> closes that check on it (no [|x|]sigma walk of its own in the
+// per-item batch path; k_decomp.hip keeps the explicit kernels for the paths that need the verdict first).
 // kilic Engine.AddPair / AddPairInv [ext] via kyber-bls12381 ValidatePairing.
+#include <type_traits>
+
 #include "kcommon.h"
 #include "testops.h"
 
@@ -53,10 +58,19 @@ struct g2proj_lds {
   }
 };
 
+// CHECK: the k == 1 workgroups (the pair (-g1, sigma)) also close sigma's psi subgroup check on their
+// own T, which is [|x|]sigma when the loop ends (pairing.h miller_t_in_subgroup), and write
+// cls[g] = REJ_NOT_IN_SUBGROUP on a failure: the per-item batch path, whose head then only decodes.
+// k_miller_f / k_miller_f_tri and the final exponentiation launch later on the same stream and skip
+// cls != REJ_OK. The k == 0 workgroup of the same items may read cls[g] before or after that byte
+// store; either is correct, since nothing reads the lines of a rejected item. Without CHECK the kernel
+// is the plain one (cls read-only): the randomized path's sums of points that were already checked.
+template <bool CHECK>
 BLS_KERNEL(BLS_WPE_LINES)
 k_miller_lines(const uint32_t* pk_tab, const uint8_t* pk_inf, const uint32_t* pk_idx, const uint32_t* H,
-               const uint8_t* h_inf, const uint32_t* S, const uint8_t* s_inf, const uint8_t* cls, size_t cnt,
-               size_t base, size_t m, size_t sub, uint32_t* LN) {
+               const uint8_t* h_inf, const uint32_t* S, const uint8_t* s_inf,
+               std::conditional_t<CHECK, uint8_t*, const uint8_t*> cls, size_t cnt, size_t base, size_t m, size_t sub,
+               uint32_t* LN) {
   const int k = (int)(blockIdx.x & 1u);
   const size_t i = (size_t)(blockIdx.x >> 1) * TPB + threadIdx.x;
   if (i >= m) return;
@@ -112,6 +126,14 @@ k_miller_lines(const uint32_t* pk_tab, const uint8_t* pk_inf, const uint32_t* pk
       if ((BLS_X_ABS >> b) & 1ull) {
         miller_add_step_ts(T, load_q, put, xp, yp);
         step++;
+      }
+    }
+    if constexpr (CHECK) {
+      // k is uniform over the workgroup: no divergence with the other pair
+      if (k == 1 && !miller_t_in_subgroup(T, load_q)) {
+        size_t j = g;
+        asm volatile("" : "+v"(j));  // the byte's address formed here, not kept across the loop
+        cls[j] = REJ_NOT_IN_SUBGROUP;
       }
     }
   }
@@ -330,13 +352,17 @@ bool launch_test_op_mf(int op, const uint32_t* in, size_t cnt, uint32_t* out, hi
 // The line staging (MILLER_LINE_WORDS per beacon) holds `sub` beacons; the chunk runs in sub-chunks
 // (one when sub >= cnt, which is what the host does: every sub-chunk adds a wave tail to both passes).
 void launch_miller(const uint32_t* pk_tab, const uint8_t* pk_inf, const uint32_t* pk_idx, const uint32_t* H,
-                   const uint8_t* h_inf, const uint32_t* S, const uint8_t* s_inf, const uint8_t* cls, size_t cnt,
-                   uint32_t* F, uint32_t* LN, size_t sub, uint32_t* park, hipStream_t st) {
+                   const uint8_t* h_inf, const uint32_t* S, const uint8_t* s_inf, uint8_t* cls, size_t cnt,
+                   uint32_t* F, uint32_t* LN, size_t sub, uint32_t* park, bool check_subgroup, hipStream_t st) {
   if (!cnt) return;
   for (size_t b = 0; b < cnt; b += sub) {
     const size_t m = cnt - b < sub ? cnt - b : sub;
-    hipLaunchKernelGGL(k_miller_lines, dim3(2 * grid_for(m)), dim3(TPB), 0, st, pk_tab, pk_inf, pk_idx, H, h_inf,
-                       S, s_inf, cls, cnt, b, m, sub, LN);
+    if (check_subgroup)
+      hipLaunchKernelGGL(k_miller_lines<true>, dim3(2 * grid_for(m)), dim3(TPB), 0, st, pk_tab, pk_inf, pk_idx, H,
+                         h_inf, S, s_inf, cls, cnt, b, m, sub, LN);
+    else
+      hipLaunchKernelGGL(k_miller_lines<false>, dim3(2 * grid_for(m)), dim3(TPB), 0, st, pk_tab, pk_inf, pk_idx, H,
+                         h_inf, S, s_inf, (const uint8_t*)cls, cnt, b, m, sub, LN);
     // Below one full wave round of the single-lane pass (1 wave/SIMD x 1024 SIMDs x 64 lanes) the GPU is
     // not full and latency decides: the 3-lane pass runs 27.6 k instructions per lane-step against
     // 73.7 k. At full occupancy the single-lane pass has the higher throughput (profiles/r02_*).

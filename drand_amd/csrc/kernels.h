@@ -1,8 +1,10 @@
 // Kernel launchers of the beacon-verification engine (host-callable, defined in k_*.hip).
 // Stage pipeline for a batch of beacons (each stage one lane per beacon, SoA staging in HBM):
 //   hash   : message derivation + hash-to-G2            -> H[i]  (affine, 4 Fp slots) + h_inf[i]
-//   decomp : sigma decompression + psi subgroup check    -> S[i]  (affine, 4 Fp slots) + s_inf[i], cls[i]
-//   miller : e(pk_i, H_i) * e(-g1, S_i) multi-Miller loop -> F[i]  (Fp12, 12 Fp slots)
+//   decomp : sigma decompression                          -> S[i]  (affine, 4 Fp slots) + s_inf[i], cls[i]
+//            (+ the psi subgroup check as kernels of its own on the randomized and timelock paths)
+//   miller : e(pk_i, H_i) * e(-g1, S_i) multi-Miller loop -> F[i]  (Fp12, 12 Fp slots); the per-item path
+//            closes S_i's psi subgroup check on the loop's own [|x|]S_i -> cls[i]
 //   fexp   : final exponentiation, == 1                  -> cls[i] (REJ_PAIRING on mismatch)
 //   finish : verdict bitmap (ballot) + first bad index (atomicMin)
 #pragma once
@@ -48,10 +50,13 @@ void launch_decompress_g2(const uint8_t* sigs, size_t stride, size_t offset, siz
 // pk for item i: pk_tab[pk_idx ? pk_idx[i] : 0] (G1_WORDS each) with pk_inf flags
 // LN: line staging for `sub` beacons (MILLER_LINE_WORDS each); the chunk runs in sub-chunks of `sub`
 // (the host passes the whole chunk: blsverify.cpp kLineSub)
+// check_subgroup: the lines pass also closes S_i's psi subgroup check on its own [|x|]S_i and writes
+// cls[i] = REJ_NOT_IN_SUBGROUP where it fails (for S decoded by launch_decompress_g2_only); without
+// it cls is only read
 constexpr int MILLER_LINE_WORDS = 68 * 2 * 6 * 12;
 void launch_miller(const uint32_t* pk_tab, const uint8_t* pk_inf, const uint32_t* pk_idx, const uint32_t* H,
-                   const uint8_t* h_inf, const uint32_t* S, const uint8_t* s_inf, const uint8_t* cls, size_t cnt,
-                   uint32_t* F, uint32_t* LN, size_t sub, uint32_t* park, hipStream_t st);
+                   const uint8_t* h_inf, const uint32_t* S, const uint8_t* s_inf, uint8_t* cls, size_t cnt,
+                   uint32_t* F, uint32_t* LN, size_t sub, uint32_t* park, bool check_subgroup, hipStream_t st);
 // park: TRI_PARK_WORDS(sub) words of scratch for the 3-lane f pass (48 words per lane, 21 items per wave)
 constexpr size_t TRI_PARK_WORDS(size_t items) { return 48 * 64 * ((items + 20) / 21); }
 // F is clobbered; W = 3 * cnt * F_WORDS words of staging; out (optional, test hook): the
@@ -124,8 +129,10 @@ void launch_pubpoly_eval(const uint32_t* commits, const uint8_t* commit_inf, uin
 // decode only on the latency engine (k_lat.hip; one two-wave workgroup per signature)
 void launch_lat_decode(const uint8_t* sigs, size_t stride, size_t offset, size_t cnt, uint32_t* S, uint8_t* s_inf,
                        uint8_t* cls, hipStream_t st);
-void launch_decompress_g2_only(const uint8_t* sigs, size_t stride, size_t offset, size_t cnt, uint32_t* S,
-                               uint8_t* s_inf, uint8_t* cls, hipStream_t st);
+// decoding alone (signatures at sigs + (base+i)*stride + offset): the subgroup check is left to
+// launch_miller(check_subgroup = true)
+void launch_decompress_g2_only(const uint8_t* sigs, size_t stride, size_t offset, size_t base, size_t cnt,
+                               uint32_t* S, uint8_t* s_inf, uint8_t* cls, hipStream_t st);
 // sum_i [lambda_i] S_i over the selected affine staging entries sel[i] (S in SoA of stride n_s),
 // compressed to 96 bytes
 // [lambda_i] S_sel[i] summed and compressed (k_latrec.hip, lane form); scratch >= t * 192 words

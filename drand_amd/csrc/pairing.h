@@ -134,6 +134,32 @@ DI void miller_add_step_ts(const TS& t, Q qload, Put put, XP xp, YP yp) {
   t.set(2, fp2_mul_inl(t.get(2), E));  // Z3
 }
 
+// The psi subgroup check of Q closed on the loop's own T. After the 63 doublings and 5 additions of
+// miller_dbl_step_ts / miller_add_step_ts over |x|'s bits, T = (X : Y : Z) is [|x|]Q in homogeneous
+// coordinates, so psi(Q) == [x]Q (x < 0; curve.h g2_in_subgroup) reads
+//     Z != 0,  X == psi(Q).x Z,  -Y == psi(Q).y Z      (Z, not Z^2 / Z^3: T is not Jacobian)
+// with psi(Q) = (conj(x) PSI_KX, conj(y) PSI_KY). The steps handle no exceptional case, and each of
+// theirs (doubling a point with Y = 0, adding to T = infinity, adding with T = +-Q) gives Z3 = 0, which
+// then stays: the doubling's Z3 = B H has H = 2 Y Z, the addition's Z3 = Z E. Such a case means
+// [k]Q = infinity for some 0 < k < 2^64, which a Q of order r never meets, so Z == 0 rejects exactly
+// the points it should. Q is re-read through qload (once per coordinate), T through its accessor.
+template <typename TS, typename Q>
+DI bool miller_t_in_subgroup(const TS& t, Q qload) {
+  bool ok = !fp2_is_zero(t.get(2));
+  {
+    const fp2 px = fp2_mul_inl(fp2_conj(qload().x), fp2_load_const(PSI_KX));
+    BLS_SCHED_FENCE();
+    ok &= fp2_eq(t.get(0), fp2_mul_inl(px, t.get(2)));
+  }
+  BLS_SCHED_FENCE();
+  {
+    const fp2 py = fp2_mul_inl(fp2_conj(qload().y), fp2_load_const(PSI_KY));
+    BLS_SCHED_FENCE();
+    ok &= fp2_eq(fp2_neg(t.get(1)), fp2_mul_inl(py, t.get(2)));
+  }
+  return ok;
+}
+
 template <typename Put, typename XP, typename YP>
 DI void miller_dbl_step_inl(g2proj& t, Put put, XP xp, YP yp) {
   miller_dbl_step_ts(g2proj_reg{t}, put, xp, yp);

@@ -1,7 +1,10 @@
 // Op counter + CPU run of the engine's own device algorithms (drand_amd/csrc/*.h compiled for the host
 // with -DBLS_HOST). Counts Montgomery multiplications (fp_mul_u12 calls; 288 32x32->64 limb products
 // each: 144 for a*b + 144 for m*p in CIOS) per pipeline stage for ONE chained beacon, and checks that
-// the beacon verifies. The counts are the algorithmic work figures used for bench.py's roofline
+// the beacon verifies. The stages are the batch path's: decompression is the decoding alone, and the
+// signature's subgroup check is the closing test on the Miller lines' own [|x|]sigma, counted under
+// Miller (`subgroup` runs that check on points from stdin beside g2_decompress's own).
+// The counts are the algorithmic work figures used for bench.py's roofline
 // (DESIGN.md §Roofline). Build + run: make -C tools opcount && tools/opcount <pk48hex> <round> <prevhex> <sighex>
 #include <cstdio>
 #include <cstdlib>
@@ -653,7 +656,51 @@ static int cmd_tlock(const char* sighex) {
   return lines_match ? 0 : 1;
 }
 
+// The batch path's subgroup check of a decoded sigma (not infinity): the call-free line steps of
+// k_miller_lines over |x|'s bits (the lines themselves dropped; they do not depend on the check) and
+// pairing.h miller_t_in_subgroup on the T they leave. close_muls: the Fp products of that closing test.
+static bool lines_subgroup_check(const g2a& Q, unsigned long long* close_muls = nullptr) {
+  g2proj T = {Q.x, Q.y, fp2_one()};
+  const g2proj_reg ts{T};
+  auto put = [](int, const fp2&) {};
+  auto xp = []() { return fp_load_const(G1_GEN_X); };
+  auto yp = []() { return fp_load_const(G1_GEN_NEG_Y); };
+  auto q = [&]() { return Q; };
+  for (int b = 62; b >= 0; b--) {
+    miller_dbl_step_ts(ts, put, xp, yp);
+    if ((BLS_X_ABS >> b) & 1ull) miller_add_step_ts(ts, q, put, xp, yp);
+  }
+  const unsigned long long c0 = g_fp_mul_count;
+  const bool in = miller_t_in_subgroup(ts, q);
+  if (close_muls) *close_muls = g_fp_mul_count - c0;
+  return in;
+}
+
+// subgroup: one 96-byte compressed G2 point in hex per line on stdin. Prints per line
+// "<batch> <ref>": the class the batch path gives (g2_decompress without its subgroup check, then
+// lines_subgroup_check) beside the class of g2_decompress with the psi check of curve.h.
+static int cmd_subgroup() {
+  static char line[512];
+  int differ = 0;
+  while (fgets(line, sizeof line, stdin)) {
+    char* save = nullptr;
+    const char* sh = strtok_r(line, " \n", &save);
+    if (!sh) continue;
+    const auto sig = unhex(sh);
+    if (sig.size() != 96) return 2;
+    g2a s, r;
+    bool sinf, rinf;
+    uint8_t cls = g2_decompress(sig.data(), s, sinf, false);
+    if (cls == REJ_OK && !sinf && !lines_subgroup_check(s)) cls = REJ_NOT_IN_SUBGROUP;
+    const uint8_t ref = g2_decompress(sig.data(), r, rinf, true);
+    printf("%d %d\n", (int)cls, (int)ref);
+    differ |= cls != ref;
+  }
+  return differ;
+}
+
 int main(int argc, char** argv) {
+  if (argc == 2 && !strcmp(argv[1], "subgroup")) return cmd_subgroup();
   if (argc == 3 && !strcmp(argv[1], "tlock")) return cmd_tlock(argv[2]);
   if (argc == 4 && !strcmp(argv[1], "rlc")) return cmd_rlc(argv[2], strtoul(argv[3], nullptr, 10));
   if (argc >= 2 && !strcmp(argv[1], "ops")) return cmd_ops(argc == 3 && !strcmp(argv[2], "list"));
@@ -665,8 +712,9 @@ int main(int argc, char** argv) {
   if (argc == 3 && !strcmp(argv[1], "f6fuzz")) return cmd_f6fuzz(strtoul(argv[2], nullptr, 10));
   if (argc != 5) {
     fprintf(stderr, "usage: %s pk48hex round prevhex|- sig96hex   (prev '-' = unchained V2)\n       %s hash msghex\n"
-            "       %s tlock sig96hex   (one compressed U in hex per line on stdin)\n",
-            argv[0], argv[0], argv[0]);
+            "       %s tlock sig96hex   (one compressed U in hex per line on stdin)\n"
+            "       %s subgroup   (one compressed G2 point in hex per line on stdin)\n",
+            argv[0], argv[0], argv[0], argv[0]);
     return 2;
   }
   auto pk = unhex(argv[1]);
@@ -693,8 +741,12 @@ int main(int argc, char** argv) {
   c0 = g_fp_mul_count;
   g2a s;
   bool sinf;
-  uint8_t cls = g2_decompress(sig.data(), s, sinf, true);
+  // the batch path: decoding alone; the subgroup check is closed on the Miller lines' own [|x|]sigma
+  // (k_miller_lines<true>), so its walk costs nothing beyond the closing test, counted under Miller
+  uint8_t cls = g2_decompress(sig.data(), s, sinf, false);
   unsigned long long n_decomp = g_fp_mul_count - c0;
+  unsigned long long n_close = 0;
+  if (cls == REJ_OK && !sinf && !lines_subgroup_check(s, &n_close)) cls = REJ_NOT_IN_SUBGROUP;
   if (cls) {
     printf("{\"verified\": false, \"class\": %d}\n", cls);
     return 1;
@@ -728,6 +780,6 @@ int main(int argc, char** argv) {
 
   printf("{\"verified\": %s, \"fp_mul\": {\"hash\": %llu, \"decompress\": %llu, \"miller\": %llu, \"final_exp\": %llu},"
          " \"limb_products_per_fp_mul\": 288}\n",
-         ok ? "true" : "false", n_hash, n_decomp, n_miller, n_fexp);
+         ok ? "true" : "false", n_hash, n_decomp, n_miller + n_close, n_fexp);
   return ok ? 0 : 1;
 }
