@@ -1,5 +1,6 @@
 // Internal to libblsverify.so (never installed, no C ABI): the context object and the helpers the
-// C-ABI entry points (blsverify.cpp) and the thread-safe service (service.cpp) share.
+// C-ABI entry points (blsverify.cpp, verify.cpp, threshold.cpp, tlock.cpp, testhooks.cpp; their shared
+// internals are host_internal.h) and the thread-safe service (service.cpp) share.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -201,7 +202,7 @@ struct blsv_ctx {
   hipStream_t side = nullptr;
   hipEvent_t fork_ev = nullptr, join_ev = nullptr;
   // the speculative VerifyRecovered's hash-to-G2 of its message from the start of a threshold round
-  // (blsverify.cpp spec_recover_launch, launch_lat_hash_key): a second side stream, joined into `side`
+  // (threshold.cpp spec_recover_launch, launch_lat_hash_key): a second side stream, joined into `side`
   // through hash_ev[slot]. Three streams in all: the boxes run 4 hardware queues per process.
   hipStream_t side2 = nullptr;
   hipEvent_t hash_ev[2] = {nullptr, nullptr};
@@ -233,7 +234,7 @@ struct blsv_ctx {
   // append at io_up_off and wrap after a synchronisation of the stream
   PinBuf io_up, io_down;
   size_t io_up_off = 0;
-  // speculative recovery beside a round's partial verification (blsverify.cpp spec_recover_*): two
+  // speculative recovery beside a round's partial verification (threshold.cpp spec_recover_*): two
   // slots (V1, V2), each with its decoded shares, Lagrange coefficients, products and output
   struct SpecSlot {
     DBuf sig, S, s_inf, cls, sel, lam, scratch, out, vmsg, voff, vlen, vcls;

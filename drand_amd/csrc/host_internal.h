@@ -1,0 +1,155 @@
+// Internal to the HIP-side host units of libblsverify.so (blsverify.cpp, verify.cpp, threshold.cpp,
+// tlock.cpp, testhooks.cpp): the pinned small copies, stage timing, the typed view of the pipeline
+// staging with its launch wrappers, and the one pass loop every verification entry point runs.
+#pragma once
+#include <functional>
+#include <initializer_list>
+
+#include "engine_ctx.h"
+#include "hostlogic.h"
+
+#pragma GCC visibility push(hidden)  // shared between the host units, never exported
+
+// ---- blsverify.cpp: pinned small copies on the main stream
+constexpr size_t kIoCap = size_t(1) << 20;
+hipError_t h2d(blsv_ctx* c, void* dst, const void* src, size_t len);
+struct Down {
+  void* user;
+  const void* dev;
+  size_t len;
+};
+// every download enqueued, one synchronisation of the main stream, then the bytes to the callers
+hipError_t download_sync(blsv_ctx* c, std::initializer_list<Down> ds);
+
+// Brackets one stage launch with events when profiling is on (no cost otherwise).
+hipEvent_t take_event(blsv_ctx* c);
+struct StageTimer {
+  blsv_ctx* c;
+  int stage;
+  size_t items;
+  hipStream_t st;
+  hipEvent_t a = nullptr;
+  StageTimer(blsv_ctx* c_, int stage_, size_t items_, hipStream_t st_) : c(c_), stage(stage_), items(items_), st(st_) {
+    if (c->prof && (a = take_event(c))) (void)hipEventRecord(a, st);
+  }
+  ~StageTimer() {
+    if (!a) return;
+    hipEvent_t b = take_event(c);
+    if (!b) return;
+    (void)hipEventRecord(b, st);
+    c->recs.push_back({stage, items, a, b});
+  }
+};
+
+// ---- the pipeline staging, typed (engine_ctx.h says which stage owns which buffer)
+struct Staging {
+  uint32_t *H, *HQ, *S, *F, *FW, *LN;
+  uint8_t *h_inf, *s_inf, *cls;
+};
+inline Staging staging(const blsv_ctx* c) {
+  return {c->H.as<uint32_t>(),    c->HQ.as<uint32_t>(),   c->S.as<uint32_t>(),
+          c->F.as<uint32_t>(),    c->FW.as<uint32_t>(),   c->LN.as<uint32_t>(),
+          c->h_inf.as<uint8_t>(), c->s_inf.as<uint8_t>(), c->cls.as<uint8_t>()};
+}
+
+// 96-byte compressed signatures on the device: item i at d + i * stride + offset
+struct SigSrc {
+  const uint8_t* d;
+  size_t stride, offset;
+};
+// the public key of item i: tab[idx ? idx[i] : 0]
+struct PkSel {
+  const uint32_t* tab;
+  const uint8_t* inf;
+  const uint32_t* idx;  // nullptr -> entry 0
+};
+inline PkSel group_pk(const blsv_ctx* c) { return {c->commits.as<uint32_t>(), c->commit_inf.as<uint8_t>(), nullptr}; }
+
+// the hash stage of [base, base + cnt) into H (HQ between its kernels)
+inline void hash_chained(blsv_ctx* c, const blsk::ChainedSrc& src, size_t base, size_t cnt, hipStream_t st) {
+  const Staging w = staging(c);
+  blsk::launch_hash_chained(src, base, cnt, w.H, w.h_inf, w.HQ, st);
+}
+inline void hash_messages(blsv_ctx* c, const uint8_t* d_msgs, const uint64_t* d_off, const uint32_t* d_len, size_t base,
+                          size_t cnt, hipStream_t st) {
+  const Staging w = staging(c);
+  blsk::launch_hash_messages(d_msgs, d_off + base, d_len + base, cnt, w.H, w.h_inf, w.HQ, st);
+}
+// ... of the messages upload_messages staged (in_msgs, in_off, in_len)
+inline void hash_uploaded(blsv_ctx* c, size_t base, size_t cnt, hipStream_t st) {
+  hash_messages(c, c->in_msgs.as<uint8_t>(), c->in_off.as<uint64_t>(), c->in_len.as<uint32_t>(), base, cnt, st);
+}
+// the latency path over the uploaded messages; S / s_inf (optional) receive the decoded signatures
+inline void lat_uploaded(blsv_ctx* c, const SigSrc& sig, size_t cnt, const PkSel& pk, uint8_t* cls, uint32_t* S,
+                         uint8_t* s_inf, hipStream_t st) {
+  blsk::launch_lat_messages(c->in_msgs.as<uint8_t>(), c->in_off.as<uint64_t>(), c->in_len.as<uint32_t>(), sig.d,
+                            sig.stride, sig.offset, cnt, pk.tab, pk.inf, pk.idx, cls, S, s_inf, st);
+}
+// the final exponentiation of the cnt values in F (W = FW; its kept squares and 3-lane products park
+// in LN, free after the Miller stage); out (optional) captures the exponentiated values
+inline void final_exp(blsv_ctx* c, size_t cnt, uint8_t* cls, hipStream_t st, uint32_t* out = nullptr) {
+  const Staging w = staging(c);
+  blsk::launch_final_exp(w.F, w.FW, cnt, cls, st, w.LN, out);
+}
+
+// ---- verify.cpp: the pass loop
+// lat_max is clamped to the context's chunk on every path that sets it (the latency kernels write one
+// class byte per item into the chunk-sized class buffer); the min keeps the bound local anyway
+inline bool use_lat(const blsv_ctx* c, size_t n) { return n > 0 && n <= std::min(c->lat_max, c->cap); }
+inline bool use_rlc(const blsv_ctx* c, size_t n) { return n > c->lat_max && n >= 2 * c->rlc.group; }
+
+// Every pass of a batch of n items: f(base, cnt) with cnt <= cap (the staging holds one pass); stops
+// at the first non-zero return
+template <typename F>
+inline int for_each_pass(const blsv_ctx* c, size_t n, F f) {
+  for (size_t base = 0; base < n; base += c->cap) {
+    const int rc = f(base, std::min(c->cap, n - base));
+    if (rc) return rc;
+  }
+  return BLSV_OK;
+}
+
+// launches the hash stage of items [base, base + cnt) on st
+using HashFn = std::function<void(size_t base, size_t cnt, hipStream_t st)>;
+// What follows the head of a pass: the exact stages per item, or the randomized path's shared checks
+// under the call's seed (rlc_draw_seed). The exact tail's Miller lines pass closes the signatures'
+// subgroup check, so its head only decodes; the randomized tail sums signatures before any Miller
+// loop, on the strength of the head's explicit check.
+struct Tail {
+  bool randomized = false;
+  uint32_t seed[8] = {0};
+  bool fused_subgroup() const { return !randomized; }
+};
+// where a pass leaves its verdicts (device): bit base + i of bitmap, first_bad = label0 + the lowest
+// rejected index (atomic min), cls (optional) the class byte of every item of the batch
+struct PassOut {
+  uint64_t* bitmap;
+  unsigned long long* first_bad;
+  uint8_t* cls;
+  uint64_t label0;
+};
+// stages 1 and 2 of one pass (hash beside decompression); the explicit subgroup kernels run unless
+// the tail closes that check itself
+int run_head(blsv_ctx* c, const SigSrc& sig, size_t base, size_t cnt, const Tail& tail, hipStream_t st,
+             const HashFn& hash);
+// all passes of n items, each the head and then the tail; pk.idx (when given) covers the batch and is
+// sliced per pass here
+int run_passes(blsv_ctx* c, size_t n, const SigSrc& sig, const PkSel& pk, const HashFn& hash, const Tail& tail,
+               const PassOut& out, hipStream_t st);
+// the context's own output buffers for n items, sized and cleared: bitmap, first_bad, misc when with_cls
+int ctx_outputs(blsv_ctx* c, size_t n, bool with_cls, PassOut& out);
+
+// the randomized path's seed as eight big-endian words, and the combination stage of one pass
+int rlc_draw_seed(blsv_ctx* c, uint32_t (&w)[8]);
+int rlc_sums(blsv_ctx* c, size_t base, size_t cnt, const uint32_t (&seed)[8], hipStream_t st);
+
+// n signatures into in_sigs and their prevs into seeds: one prev0 (prev0_len bytes) of a continuous
+// chain, or with prev_rows a 96-byte row per round (segments of length 1: every round hashes its own)
+int stage_chain(blsv_ctx* c, uint64_t first_round, const uint8_t* prevs, size_t prev0_len, bool prev_rows,
+                const uint8_t* sigs96, size_t n, blsk::ChainedSrc& src);
+// decode cnt 48-byte G1 points into (tab, inf) on the device; their classes come back in cls
+int decode_g1(blsv_ctx* c, const uint8_t* pk48, size_t cnt, DBuf& tab, DBuf& inf, std::vector<uint8_t>& cls);
+// n messages packed back to back (msg_lens[i] bytes each) into in_msgs / in_off / in_len
+int upload_messages(blsv_ctx* c, const uint8_t* msgs, const uint32_t* msg_lens, size_t n);
+
+#pragma GCC visibility pop

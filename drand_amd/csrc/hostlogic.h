@@ -1,0 +1,271 @@
+// The host side's pure logic: bit packing, share selection, Fr / Lagrange arithmetic, layout and
+// count arithmetic. Nothing here touches HIP or blsv_ctx, so tools/hosttest.cpp runs it under the
+// sanitizers on a machine without a GPU (tests/test_sanitize.py). No HIP header may be included.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "../../include/blsverify.h"
+
+#pragma GCC visibility push(hidden)  // internal to whatever links it: never part of the library's ABI
+namespace blsv_detail {
+
+// reduce a 32-byte big-endian scalar mod r -> 8 little-endian words
+inline void scalar_mod_r(const uint8_t* be32, uint32_t out[8]) {
+  static const uint32_t R[8] = {0x00000001u, 0xffffffffu, 0xfffe5bfeu, 0x53bda402u,
+                                0x09a1d805u, 0x3339d808u, 0x299d7d48u, 0x73eda753u};
+  for (int i = 0; i < 8; i++) {
+    const uint8_t* q = be32 + 28 - 4 * i;
+    out[i] = ((uint32_t)q[0] << 24) | ((uint32_t)q[1] << 16) | ((uint32_t)q[2] << 8) | q[3];
+  }
+  for (int rep = 0; rep < 4; rep++) {  // value < 2^256 < 3r: at most 2 subtractions
+    bool ge = true;
+    for (int i = 7; i >= 0; i--) {
+      if (out[i] != R[i]) {
+        ge = out[i] > R[i];
+        break;
+      }
+    }
+    if (!ge) break;
+    uint64_t br = 0;
+    for (int i = 0; i < 8; i++) {
+      uint64_t d = (uint64_t)out[i] - R[i] - br;
+      out[i] = (uint32_t)d;
+      br = (d >> 63) & 1;
+    }
+  }
+}
+
+// ---------------------------------------------------------------- Lagrange coefficients on the host
+// kyber share.RecoverCommit's basis at 0 ([ext] drand/kyber@d59c3367dcde share/poly.go, restated) over
+// Fr for the shares x_i = index_i + 1: lambda_i = prod_{j != i} x_j / (x_j - x_i). Every factor is a
+// small integer (|x_j - x_i| < 2^16), so a coefficient is ~2t small products and the t inverses share
+// one Fermat inversion (Montgomery's trick): ~30 us for t = 33 against 0.56 ms for the serial
+// one-lane-per-coefficient device kernel this replaced, and the recovery no longer waits on it.
+namespace hfr {
+typedef unsigned __int128 u128;
+static const uint64_t RM[4] = {0xffffffff00000001ull, 0x53bda402fffe5bfeull, 0x3339d80809a1d805ull,
+                               0x73eda753299d7d48ull};
+struct E {
+  uint64_t l[4];
+};
+inline bool geq_r(const uint64_t (&a)[5]) {
+  if (a[4]) return true;
+  for (int i = 3; i >= 0; i--)
+    if (a[i] != RM[i]) return a[i] > RM[i];
+  return true;
+}
+inline void sub_r(uint64_t (&a)[5]) {
+  uint64_t br = 0;
+  for (int i = 0; i < 4; i++) {
+    const u128 d = (u128)a[i] - RM[i] - br;
+    a[i] = (uint64_t)d;
+    br = (uint64_t)(d >> 64) & 1u;
+  }
+  a[4] -= br;
+}
+inline uint64_t n0() {  // -r^-1 mod 2^64 (Newton)
+  uint64_t inv = 1;
+  for (int k = 0; k < 7; k++) inv *= 2 - RM[0] * inv;
+  return (uint64_t)0 - inv;
+}
+// a b 2^-256 mod r (CIOS), inputs and output < r
+inline E mul(const E& a, const E& b) {
+  static const uint64_t N0 = n0();
+  uint64_t t[6] = {0, 0, 0, 0, 0, 0};
+  for (int i = 0; i < 4; i++) {
+    uint64_t c = 0;
+    for (int j = 0; j < 4; j++) {
+      const u128 v = (u128)a.l[j] * b.l[i] + t[j] + c;
+      t[j] = (uint64_t)v;
+      c = (uint64_t)(v >> 64);
+    }
+    u128 v = (u128)t[4] + c;
+    t[4] = (uint64_t)v;
+    t[5] = (uint64_t)(v >> 64);
+    const uint64_t m = t[0] * N0;
+    v = (u128)m * RM[0] + t[0];
+    c = (uint64_t)(v >> 64);
+    for (int j = 1; j < 4; j++) {
+      v = (u128)m * RM[j] + t[j] + c;
+      t[j - 1] = (uint64_t)v;
+      c = (uint64_t)(v >> 64);
+    }
+    v = (u128)t[4] + c;
+    t[3] = (uint64_t)v;
+    t[4] = t[5] + (uint64_t)(v >> 64);
+  }
+  uint64_t r[5] = {t[0], t[1], t[2], t[3], t[4]};
+  if (geq_r(r)) sub_r(r);
+  return {{r[0], r[1], r[2], r[3]}};
+}
+inline E add(const E& a, const E& b) {
+  uint64_t r[5];
+  uint64_t c = 0;
+  for (int i = 0; i < 4; i++) {
+    const u128 v = (u128)a.l[i] + b.l[i] + c;
+    r[i] = (uint64_t)v;
+    c = (uint64_t)(v >> 64);
+  }
+  r[4] = c;
+  if (geq_r(r)) sub_r(r);
+  return {{r[0], r[1], r[2], r[3]}};
+}
+inline const E& r2() {  // 2^512 mod r: 1 doubled 512 times
+  static const E v = [] {
+    E x = {{1, 0, 0, 0}};
+    for (int k = 0; k < 512; k++) x = add(x, x);
+    return x;
+  }();
+  return v;
+}
+// the Montgomery form of the integer v (|v| < 2^63), negative values as r - |v|
+inline E from_int(int64_t v) {
+  E x = {{(uint64_t)(v < 0 ? -v : v), 0, 0, 0}};
+  if (v < 0) {
+    uint64_t a[5] = {RM[0], RM[1], RM[2], RM[3], 0};
+    uint64_t br = 0;
+    for (int i = 0; i < 4; i++) {
+      const u128 d = (u128)a[i] - x.l[i] - br;
+      a[i] = (uint64_t)d;
+      br = (uint64_t)(d >> 64) & 1u;
+    }
+    x = {{a[0], a[1], a[2], a[3]}};
+  }
+  return mul(x, r2());
+}
+inline E inv(const E& a) {  // a^(r - 2), Montgomery form in and out
+  uint64_t e[4] = {RM[0] - 2, RM[1], RM[2], RM[3]};
+  E acc = from_int(1);
+  for (int i = 255; i >= 0; i--) {
+    acc = mul(acc, acc);
+    if ((e[i >> 6] >> (i & 63)) & 1u) acc = mul(acc, a);
+  }
+  return acc;
+}
+}  // namespace hfr
+
+// lambda_i (plain, canonical, 8 little-endian words each) for the share indices idx[0 .. t)
+inline void host_lagrange(const uint32_t* idx, size_t t, uint32_t* out) {
+  std::vector<hfr::E> num(t), den(t), pre(t + 1);
+  for (size_t i = 0; i < t; i++) {
+    const int64_t xi = (int64_t)idx[i] + 1;
+    hfr::E n = hfr::from_int(1), d = n;
+    for (size_t j = 0; j < t; j++) {
+      if (j == i) continue;
+      const int64_t xj = (int64_t)idx[j] + 1;
+      n = hfr::mul(n, hfr::from_int(xj));
+      d = hfr::mul(d, hfr::from_int(xj - xi));
+    }
+    num[i] = n;
+    den[i] = d;
+  }
+  // Montgomery's trick: one inversion for the t denominators (none is 0: the indices are distinct)
+  pre[0] = hfr::from_int(1);
+  for (size_t i = 0; i < t; i++) pre[i + 1] = hfr::mul(pre[i], den[i]);
+  hfr::E run = hfr::inv(pre[t]);
+  const hfr::E one_plain = {{1, 0, 0, 0}};
+  for (size_t i = t; i-- > 0;) {
+    const hfr::E di = hfr::mul(run, pre[i]);  // 1 / den_i
+    run = hfr::mul(run, den[i]);
+    const hfr::E lam = hfr::mul(hfr::mul(num[i], di), one_plain);  // out of Montgomery form
+    for (int w = 0; w < 4; w++) {
+      out[i * 8 + 2 * w] = (uint32_t)lam.l[w];
+      out[i * 8 + 2 * w + 1] = (uint32_t)(lam.l[w] >> 32);
+    }
+  }
+}
+
+// ---------------------------------------------------------------- verdict bits
+// the device bitmap's 64-bit words (bit i of the batch = bit i % 64 of word i / 64) -> ceil(n / 8)
+// bytes, the bits past n cleared
+inline void bitmap_words_to_bytes(const uint64_t* w, size_t n, uint8_t* out) {
+  for (size_t i = 0; i < (n + 7) / 8; i++) {
+    uint8_t b = (uint8_t)(w[i / 8] >> (8 * (i % 8)));
+    if (i == (n + 7) / 8 - 1 && (n % 8)) b &= (uint8_t)((1u << (n % 8)) - 1);
+    out[i] = b;
+  }
+}
+
+// the latency branch's epilogue (launch_finish's rule on the host): the bitmap (optional, ceil(n / 8)
+// bytes) of the n class bytes; returns the first rejected index or UINT64_MAX
+inline uint64_t fold_classes(const uint8_t* cls, size_t n, uint8_t* ok_bitmap) {
+  uint64_t fb = UINT64_MAX;
+  for (size_t i = 0; i < n; i++) {
+    if (cls[i] != BLSV_REJ_OK && fb == UINT64_MAX) fb = i;
+    if (ok_bitmap) {
+      if (i % 8 == 0) ok_bitmap[i / 8] = 0;
+      ok_bitmap[i / 8] |= (uint8_t)((cls[i] == BLSV_REJ_OK) << (i % 8));
+    }
+  }
+  return fb;
+}
+
+// OR the first cnt bits of src (LSB first) into dst starting at bit pos
+inline void or_bits_at(uint8_t* dst, const uint8_t* src, size_t cnt, size_t pos) {
+  const size_t nb = (cnt + 7) / 8, q = pos / 8, s = pos % 8;
+  for (size_t j = 0; j < nb; j++) {
+    uint8_t b = src[j];
+    if (j == nb - 1 && (cnt % 8)) b &= (uint8_t)((1u << (cnt % 8)) - 1);
+    dst[q + j] |= (uint8_t)(b << s);
+    if (s && (b >> (8 - s))) dst[q + j + 1] |= (uint8_t)(b >> (8 - s));
+  }
+}
+
+// ---------------------------------------------------------------- threshold shares
+// the big-endian 16-bit index prefix of each of k tbls shares (0 for shares too short to hold one)
+inline void share_indices(const uint8_t* partials, size_t partial_len, size_t k, std::vector<uint32_t>& index) {
+  index.assign(k, 0);
+  if (partial_len < 2) return;
+  for (size_t i = 0; i < k; i++) index[i] = ((uint32_t)partials[i * partial_len] << 8) | partials[i * partial_len + 1];
+}
+
+// kyber tbls.Recover + share.RecoverCommit ([ext] drand/kyber@d59c3367dcde sign/tbls/tbls.go,
+// share/poly.go, restated from the published source; parity unpinned by any reference test):
+// walk the shares of items [lo, hi) in input order, skip invalid ones, keep appending valid ones until
+// t are held -- a duplicate index counts toward t; then xyCommit keys them by index (duplicates
+// collapse) and drops indices >= n. sel gets the positions and idx the indices of the shares to
+// interpolate; false when fewer than t distinct remain ("not enough good public shares").
+inline bool select_shares(const std::vector<uint8_t>& cls, const std::vector<uint32_t>& index, size_t lo, size_t hi,
+                          size_t t, size_t n, std::vector<uint32_t>& sel, std::vector<uint32_t>& idx) {
+  sel.clear();
+  idx.clear();
+  size_t taken = 0;
+  for (size_t i = lo; i < hi && taken < t; i++) {
+    if (cls[i] != BLSV_REJ_OK) continue;
+    taken++;
+    if (index[i] >= n || std::find(idx.begin(), idx.end(), index[i]) != idx.end()) continue;
+    sel.push_back((uint32_t)i);
+    idx.push_back(index[i]);
+  }
+  return sel.size() >= t;
+}
+
+// ---------------------------------------------------------------- counts and layouts
+// randomized path: the items of a pass of cnt items in its failing groups fail[0 .. nf) (ascending
+// indices of groups of G items, nf >= 1): only the last entry can be the pass's short last group
+inline size_t rlc_failing_items(size_t cnt, size_t G, const uint32_t* fail, size_t nf) {
+  const size_t ng = (cnt + G - 1) / G;
+  return nf * G - (fail[nf - 1] == ng - 1 ? ng * G - cnt : 0);
+}
+
+// svc_verify_mixed's packed upload of n items with mbytes message bytes:
+// off[n + 1] | lens[n] | idx[n] | sigs[n][96] | message bytes (8-byte aligned parts)
+struct SvcLayout {
+  size_t o_len, o_idx, o_sig, o_msg, total;
+};
+inline SvcLayout svc_layout(size_t n, size_t mbytes) {
+  SvcLayout l;
+  l.o_len = (n + 1) * 8;
+  l.o_idx = l.o_len + ((n * 4 + 7) & ~size_t(7));
+  l.o_sig = l.o_idx + ((n * 4 + 7) & ~size_t(7));
+  l.o_msg = l.o_sig + n * 96;
+  l.total = l.o_msg + mbytes + 8;
+  return l;
+}
+
+}  // namespace blsv_detail
+#pragma GCC visibility pop

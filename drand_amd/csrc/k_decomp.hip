@@ -134,7 +134,7 @@ void launch_decompress_g2(const uint8_t* sigs, size_t stride, size_t offset, siz
                      g_generic_chains_all);
 }
 
-// decoding only: the head of the per-item batch path (blsverify.cpp run_head), whose Miller lines pass
+// decoding only: the head of the per-item batch path (verify.cpp run_head), whose Miller lines pass
 // closes the subgroup check on its own [|x|]sigma (k_miller.hip k_miller_lines<true>)
 void launch_decompress_g2_only(const uint8_t* sigs, size_t stride, size_t offset, size_t base, size_t cnt,
                                uint32_t* S, uint8_t* s_inf, uint8_t* cls, hipStream_t st) {

@@ -1,5 +1,5 @@
 // Latency path: one workgroup of eight waves verifies one item end to end (wvteam.h: limbs across
-// lanes, the item's independent work across the waves). Used for small batches (blsverify.cpp routes
+// lanes, the item's independent work across the waves). Used for small batches (verify.cpp routes
 // batches up to BLSV_LAT_MAX items here), where the batch pipeline's one-lane-per-item stages would
 // leave the chip idle and pay a serial chain of ~16 M VALU instructions per lane. Same inputs and
 // reject classes as the batch stages; the verdicts then go through launch_finish like theirs.
@@ -98,7 +98,7 @@ __global__ void __launch_bounds__(64 * WV_WAVES) k_lat_messages(const uint8_t* m
              sigs + i * stride + offset, pk_tab, pk_inf, pk_idx, cls, S, s_inf, cnt);
 }
 
-// decode only (the speculative recovery's shares, blsverify.cpp spec_recover_launch): one workgroup of
+// decode only (the speculative recovery's shares, threshold.cpp spec_recover_launch): one workgroup of
 // two waves per signature, wave 0 decoding (whash.h g2_decompress, no subgroup check: validity is the
 // partials' verdict) while wave 1 multiplies for its two square roots, as the signature branch of
 // wvteam.h verify_team does; sigma lands in S (stride cnt) as k_lat_messages stores it. Replaces the
@@ -132,7 +132,7 @@ void launch_lat_decode(const uint8_t* sigs, size_t stride, size_t offset, size_t
   hipLaunchKernelGGL(k_lat_decode, dim3((unsigned)cnt), dim3(128), 0, st, sigs, stride, offset, cnt, S, s_inf, cls);
 }
 
-// the fused round's VerifyRecovered (blsverify.cpp spec_recover_launch): H(msg) and the key pair's
+// the fused round's VerifyRecovered (threshold.cpp spec_recover_launch): H(msg) and the key pair's
 // Miller loop from the start of the round, then the rest of the check against the recovered
 // signature's affine point (wvteam.h team_hash_key / verify_team_pre)
 static_assert(kLatHoutWords == (size_t)wv::HOUT_WORDS && kLatSaffWords == (size_t)wv::SAFF_WORDS, "hand-off sizes");

@@ -49,7 +49,7 @@ void launch_decompress_g2(const uint8_t* sigs, size_t stride, size_t offset, siz
                           uint8_t* s_inf, uint8_t* cls, hipStream_t st);
 // pk for item i: pk_tab[pk_idx ? pk_idx[i] : 0] (G1_WORDS each) with pk_inf flags
 // LN: line staging for `sub` beacons (MILLER_LINE_WORDS each); the chunk runs in sub-chunks of `sub`
-// (the host passes the whole chunk: blsverify.cpp kLineSub)
+// (the host passes the whole chunk: engine_ctx.h kLineSub)
 // check_subgroup: the lines pass also closes S_i's psi subgroup check on its own [|x|]S_i and writes
 // cls[i] = REJ_NOT_IN_SUBGROUP where it fails (for S decoded by launch_decompress_g2_only); without
 // it cls is only read

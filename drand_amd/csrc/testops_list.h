@@ -1,6 +1,6 @@
 // The list of raw operation hooks (testops.h holds the operations): BLS_TEST_OPS(X) with
 // X(name, Fp elements in, Fp elements out, kind); kinds as described in testops.h. No device code here,
-// so the host side of the library (blsverify.cpp) can include it.
+// so the host side of the library (testhooks.cpp) can include it.
 #pragma once
 
 #define BLS_TEST_OPS(X)                                                                              \

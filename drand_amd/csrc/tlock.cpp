@@ -1,0 +1,136 @@
+// Timelock opening: blsv_tlock_open* (include/blsverify.h "timelock", tlock.h). Sigma is prepared once
+// and cached, then per pass the U decode, the f pass against sigma's line table, the final
+// exponentiation with its capture output and the Gt encoding, all in the pipeline staging
+// (engine_ctx.h lists which buffer holds what). It shares the staging with the verification passes
+// (verify.cpp) but none of their stages, so it keeps a pass loop of its own.
+#include "host_internal.h"
+
+// Decodes and prepares sigma on st unless it is the cached one; its class is read back (the one
+// synchronisation of a call, and only on a new sigma).
+static int tlock_prepare_sig(blsv_ctx* c, const uint8_t* sig96, hipStream_t st, uint8_t* sig_class) {
+  tlock_state& t = c->tlock;
+  if (!t.valid || memcmp(t.sig, sig96, 96) != 0) {
+    t.valid = false;
+    HIPCHK(c, t.d_sig.ensure(96));
+    HIPCHK(c, t.S.ensure(blsk::S_WORDS * 4));
+    HIPCHK(c, t.s_inf.ensure(1));
+    HIPCHK(c, t.s_cls.ensure(1));
+    HIPCHK(c, t.tab.ensure(blsk::kTlockTabWords * 4));
+    HIPCHK(c, hipMemcpyAsync(t.d_sig.p, sig96, 96, hipMemcpyHostToDevice, st));
+    {
+      StageTimer tm(c, ST_TLOCK, 1, st);
+      blsk::launch_decompress_g2(t.d_sig.as<uint8_t>(), 96, 0, 0, 1, t.S.as<uint32_t>(), t.s_inf.as<uint8_t>(),
+                                 t.s_cls.as<uint8_t>(), st);
+      blsk::launch_tlock_prepare(t.S.as<uint32_t>(), t.s_inf.as<uint8_t>(), t.s_cls.as<uint8_t>(),
+                                 t.tab.as<uint32_t>(), st);
+    }
+    HIPCHK(c, hipGetLastError());
+    uint8_t cls = 0xff;
+    HIPCHK(c, hipMemcpyAsync(&cls, t.s_cls.p, 1, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    memcpy(t.sig, sig96, 96);
+    t.cls = cls;
+    t.valid = true;
+    if (cls == BLSV_REJ_OK) t.prepared++;
+  }
+  if (sig_class) *sig_class = t.cls;
+  if (t.cls != BLSV_REJ_OK) return fail(c, BLSV_EINVAL, "tlock_open: signature rejected (class %d)", (int)t.cls);
+  return BLSV_OK;
+}
+
+// One pass of cnt <= cap items: d_us (cnt x 48 bytes) -> d_out (cnt x 576 bytes), classes in s_inf
+static int tlock_pass(blsv_ctx* c, const uint8_t* d_us, size_t cnt, uint8_t* d_out, uint8_t* d_cls_out,
+                      hipStream_t st) {
+  const tlock_state& t = c->tlock;
+  const Staging w = staging(c);
+  uint32_t* U = w.H;
+  uint8_t* u_inf = w.h_inf;
+  uint8_t* ucls = w.s_inf;
+  {
+    StageTimer tm(c, ST_DECOMP, cnt, st);
+    blsk::launch_decompress_g1(d_us, cnt, U, u_inf, ucls, st);
+  }
+  // the final exponentiation marks a value other than 1 in the class bytes it is given: it gets a copy
+  HIPCHK(c, hipMemcpyAsync(w.cls, ucls, cnt, hipMemcpyDeviceToDevice, st));
+  {
+    StageTimer tm(c, ST_TLOCK, cnt, st);
+    blsk::launch_tlock_f(t.tab.as<uint32_t>(), U, u_inf, ucls, t.s_inf.as<uint8_t>(), cnt, w.F, st);
+  }
+  {
+    StageTimer tm(c, ST_FEXP, cnt, st);
+    final_exp(c, cnt, w.cls, st, w.HQ);
+  }
+  blsk::launch_tlock_encode(w.HQ, ucls, cnt, d_out, st);
+  if (d_cls_out) HIPCHK(c, hipMemcpyAsync(d_cls_out, ucls, cnt, hipMemcpyDeviceToDevice, st));
+  HIPCHK(c, hipGetLastError());
+  return BLSV_OK;
+}
+
+// Every pass of n items under the prepared sigma. Device buffers (host == false): us, out and cls
+// (optional) are read and written in place on st. Host buffers: a pass's compressed U bytes travel in
+// S, its encoded values come back through F, and each pass ends with the download's synchronisation.
+static int tlock_passes(blsv_ctx* c, bool host, const uint8_t* us, size_t n, uint8_t* out, uint8_t* cls,
+                        hipStream_t st) {
+  int rc = ensure_workspace(c, n);
+  if (rc) return rc;
+  for (size_t base = 0; base < n; base += c->cap) {
+    const size_t cnt = std::min(c->cap, n - base);
+    const uint8_t* pass_us = us + base * BLSV_U_LEN;
+    uint8_t* pass_out = out + base * BLSV_GT_LEN;
+    if (host) {
+      HIPCHK(c, h2d(c, c->S.p, pass_us, cnt * BLSV_U_LEN));
+      rc = tlock_pass(c, c->S.as<uint8_t>(), cnt, c->F.as<uint8_t>(), nullptr, st);
+      if (rc) return rc;
+      HIPCHK(c, download_sync(c, {{pass_out, c->F.p, cnt * BLSV_GT_LEN}, {cls + base, c->s_inf.p, cnt}}));
+    } else {
+      rc = tlock_pass(c, pass_us, cnt, pass_out, cls ? cls + base : nullptr, st);
+      if (rc) return rc;
+    }
+  }
+  c->tlock.items += n;
+  return BLSV_OK;
+}
+
+extern "C" {
+
+int blsv_tlock_open(blsv_ctx* c, const uint8_t* sig96, const uint8_t* us48, size_t n, uint8_t* out_gt576, uint8_t* ok,
+                    uint8_t* reject_class, uint8_t* sig_class) {
+  if (!c) return BLSV_EINVAL;
+  if (!sig96 || (n && (!us48 || !out_gt576 || !ok))) return fail(c, BLSV_EINVAL, "tlock_open: bad arguments");
+  (void)hipSetDevice(c->device);
+  int rc = tlock_prepare_sig(c, sig96, c->stream, sig_class);
+  if (rc) return rc;
+  if (!n) return BLSV_OK;
+  std::vector<uint8_t> own;
+  uint8_t* cls = reject_class;
+  if (!cls) {
+    own.resize(n);
+    cls = own.data();
+  }
+  rc = tlock_passes(c, true, us48, n, out_gt576, cls, c->stream);
+  if (rc) return rc;
+  for (size_t i = 0; i < n; i++) ok[i] = cls[i] == BLSV_REJ_OK;
+  return BLSV_OK;
+}
+
+int blsv_tlock_open_dev(blsv_ctx* c, const uint8_t* sig96, const uint8_t* d_us48, size_t n, uint8_t* d_out_gt576,
+                        uint8_t* d_reject_class, void* stream) {
+  if (!c) return BLSV_EINVAL;
+  if (!sig96 || (n && (!d_us48 || !d_out_gt576)) || ((uintptr_t)d_out_gt576 & 3))
+    return fail(c, BLSV_EINVAL, "tlock_open_dev: bad arguments");
+  (void)hipSetDevice(c->device);
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  int rc = tlock_prepare_sig(c, sig96, st, nullptr);
+  if (rc) return rc;
+  if (!n) return BLSV_OK;
+  return tlock_passes(c, false, d_us48, n, d_out_gt576, d_reject_class, st);
+}
+
+int blsv_tlock_stats(blsv_ctx* c, uint64_t* prepared, uint64_t* items) {
+  if (!c) return BLSV_EINVAL;
+  if (prepared) *prepared = c->tlock.prepared;
+  if (items) *items = c->tlock.items;
+  return BLSV_OK;
+}
+
+}  // extern "C"

@@ -3,7 +3,7 @@
 // 25-bit limbs, dot products with one Montgomery reduction), wtower.h (Fp12 as six w-power
 // coefficients), wcurve.h (G2 Jacobian), whash.h (hash-to-G2, G2 decompression), wpairing.h (Miller
 // loop, final exponentiation). The batch engine (fp.h ... pairing.h, one lane per beacon) stays the
-// throughput path; blsverify.cpp routes small batches here.
+// throughput path; verify.cpp routes small batches here.
 #pragma once
 #include "wpairing.h"
 

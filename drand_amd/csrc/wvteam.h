@@ -881,7 +881,7 @@ WVI uint8_t verify_team(const uint8_t* sig, const uint32_t (&b0)[8], const uint3
 
 
 // ------------------------------------------------------------------ VerifyRecovered in two launches
-// The fused threshold round (blsverify.cpp spec_recover_launch) verifies the signature it recovers
+// The fused threshold round (threshold.cpp spec_recover_launch) verifies the signature it recovers
 // speculatively. Its message and the group key are known from the start, so phase A's hash branch
 // and then phase B's key-pair Miller loop run as their own launch (team_hash_key) beside the partial
 // verification and the recovery; the recovered signature reaches the check as the affine point the

@@ -11,7 +11,12 @@ Recipe: client/test/result/mock/result.go:98-132 with the golden chained key and
 sha256(sig_{i-1} || BE64(i)). Signed by the C oracle (oracle/c/bls_oracle.c, pinned to the
 reference KAT key/curve_test.go:10-30 in tests/test_oracle_c.py); the script re-verifies samples.
 
-Usage: python tests/golden/make_chain_fixture.py   (~20 s)
+chain16449_a.bin + chain16449_b.bin (each under 1 MiB): the same recipe for 16,384 + 65 rounds from
+round 5 (the genesis seed as round 5's PreviousSig), the smallest history that crosses a pass boundary
+of the HOST entry points at the smallest chunk (tests/test_gpu_passes.py). blsv_generate_chained_dev
+signs such a chain on one lane, 18 ms a round: 5 minutes on the test box, against 2 here, once.
+
+Usage: python tests/golden/make_chain_fixture.py   (~20 s + ~2 min)
 """
 from __future__ import annotations
 
@@ -47,6 +52,19 @@ def main():
     with open(OUT, "wb") as f:
         f.write(b"".join(sigs))
     print("wrote", OUT, N, "signatures")
+    # the two-pass history of tests/test_gpu_passes.py
+    n, first = 16384 + 65, 5
+    sigs, prev = [], seed
+    for r in range(first, first + n):
+        prev = c_oracle.sign(sk, hashlib.sha256(prev + r.to_bytes(8, "big")).digest())
+        sigs.append(prev)
+    for lo in (0, 16380, n - 9):
+        assert c_oracle.verify_chained(pk, first + lo, sigs[lo - 1] if lo else seed, b"".join(sigs[lo:lo + 9])) == [0] * 9
+    half = (n + 1) // 2
+    for name, part in (("chain16449_a.bin", sigs[:half]), ("chain16449_b.bin", sigs[half:])):
+        with open(os.path.join(HERE, name), "wb") as f:
+            f.write(b"".join(part))
+    print("wrote chain16449_a.bin, chain16449_b.bin:", n, "signatures from round", first)
 
 
 if __name__ == "__main__":

@@ -40,7 +40,7 @@ def test_library_exports_every_symbol():
 
 def test_host_lagrange_matches_integers():
     """blsv_test_lagrange (the host Lagrange basis blsv_recover / blsv_aggregate* interpolate with,
-    blsverify.cpp host_lagrange) against Python integers: lambda_i = prod x_j / (x_j - x_i) mod r,
+    hostlogic.h host_lagrange) against Python integers: lambda_i = prod x_j / (x_j - x_i) mod r,
     x = index + 1, for the golden round's first 33 shares, a scattered set and t = 1; repeated indices
     are refused. No GPU: the function is host arithmetic."""
     if not os.path.exists(_lib.LIB_PATH):

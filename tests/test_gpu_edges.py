@@ -125,7 +125,7 @@ def test_aggregate_round(engine, golden):
     engine.set_group([bytes.fromhex(c) for c in th["commits"]], th["n"])
     msg = bytes.fromhex(th["msg"])
     partials = [bytes.fromhex(p) for p in th["partials"]]
-    # the recovery is speculated beside the partials' verification (blsverify.cpp spec_recover_*):
+    # the recovery is speculated beside the partials' verification (threshold.cpp spec_recover_*):
     # kept when every selected share verifies, recomputed from the valid shares otherwise
     h0, m0 = engine.spec_stats()
     ok, cls, sig, gok = engine.aggregate(msg, partials, th["t"], th["n"])

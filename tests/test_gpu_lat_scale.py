@@ -29,7 +29,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NONE = (1 << 64) - 1
 BIG = 1 << 20
-LAT_MAX = 1536  # blsverify.cpp kLatMaxDefault (test_default_cutover)
+LAT_MAX = 1536  # engine_ctx.h kLatMaxDefault (test_default_cutover)
 
 # classes of the mixed golden (tests/golden/golden.json "mixed"): name -> source index there; the
 # decode classes are copied as bytes, the others are made from the local signature

@@ -107,3 +107,23 @@ def test_chain2049_fixture_is_the_golden_chain(golden):
     pk = bytes.fromhex(ch["pk"])
     for lo in (1999, 2047):
         assert c_oracle.verify_chained(pk, lo + 1, raw[(lo - 1) * 96:lo * 96], raw[lo * 96:(lo + 2) * 96]) == [0, 0]
+
+
+def test_chain16449_fixture_is_one_chain_from_round_5(golden):
+    """tests/golden/chain16449_{a,b}.bin (make_chain_fixture.py): 16,384 + 65 rounds from round 5 with the
+    genesis seed as round 5's previous signature; the C oracle accepts the first rounds, the rounds across
+    the file split and the pass boundary of tests/test_gpu_passes.py, and the last ones."""
+    from oracle import c_oracle
+
+    c_oracle.load()
+    raw = b""
+    for part in ("chain16449_a.bin", "chain16449_b.bin"):
+        with open(os.path.join(os.path.dirname(__file__), "golden", part), "rb") as f:
+            raw += f.read()
+    n, first = 16384 + 65, 5
+    assert len(raw) == n * 96
+    ch = golden["chained"]
+    pk = bytes.fromhex(ch["pk"])
+    assert c_oracle.verify_chained(pk, first, bytes.fromhex(ch["genesis_seed"]), raw[:3 * 96]) == [0] * 3
+    for lo in (8223, 16382, n - 3):
+        assert c_oracle.verify_chained(pk, first + lo, raw[(lo - 1) * 96:lo * 96], raw[lo * 96:(lo + 3) * 96]) == [0] * 3

@@ -7,6 +7,10 @@
 //   boltload  the drand.db loader (drand_amd/csrc/boltload.cpp, include/boltload.h) over the files
 //             named on the command line (written by tests/support/boltwriter.py), plus truncated and
 //             bit-flipped copies of each: every call must fail cleanly or succeed, never fault.
+//   hostlogic the pure host logic of the HIP-side units (drand_amd/csrc/hostlogic.h: bit packing,
+//             share selection, Fr / Lagrange arithmetic, counts and layouts) on fixed cases, every
+//             buffer heap-allocated at the size its caller gives it; the results go out as one JSON
+//             line that tests/test_sanitize.py compares with values computed in Python.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -20,6 +24,7 @@
 #include <vector>
 
 #include "../drand_amd/csrc/coalesce.h"
+#include "../drand_amd/csrc/hostlogic.h"
 #include "../include/boltload.h"
 
 using blsv_detail::Coalescer;
@@ -200,13 +205,164 @@ int test_boltload(int argc, char** argv) {
   return 0;
 }
 
+std::string hex(const uint8_t* p, size_t n) {
+  static const char* d = "0123456789abcdef";
+  std::string s;
+  for (size_t i = 0; i < n; i++) {
+    s += d[p[i] >> 4];
+    s += d[p[i] & 15];
+  }
+  return s;
+}
+
+std::string list_of(const std::vector<uint32_t>& v) {
+  std::string s = "[";
+  for (size_t i = 0; i < v.size(); i++) s += (i ? "," : "") + std::to_string(v[i]);
+  return s + "]";
+}
+
+// The cases are fixed here and restated in tests/test_sanitize.py (test_hostlogic_asan), which computes
+// every expected value itself.
+int test_hostlogic() {
+  using namespace blsv_detail;
+  const size_t sizes[] = {1, 7, 8, 9, 63, 64, 65, 127, 128, 129};
+  std::string out = "{\"hostlogic\": {\"verdicts\": [";
+  bool first = true;
+  for (size_t n : sizes)
+    for (size_t rej : {size_t(0), n - 1, n / 2, n}) {
+      // one reject at 0, n - 1 or the middle, then all three (rej == n); the device words carry garbage
+      // above bit n
+      std::vector<uint8_t> cls(n, BLSV_REJ_OK);
+      if (rej < n)
+        cls[rej] = BLSV_REJ_PAIRING;
+      else
+        cls[0] = cls[n - 1] = cls[n / 2] = BLSV_REJ_PAIRING;
+      const size_t words = (n + 63) / 64, nb = (n + 7) / 8;
+      std::vector<uint64_t> w(words + 1, 0);  // the host driver's download buffer
+      for (size_t i = 0; i < 64 * words; i++)
+        if (i >= n || cls[i] == BLSV_REJ_OK) w[i / 64] |= uint64_t(1) << (i % 64);
+      std::vector<uint8_t> guarded(nb + 2, 0xEE), exact(nb), folded(nb + 2, 0xEE), folded_exact(nb, 0xEE);
+      bitmap_words_to_bytes(w.data(), n, guarded.data());
+      bitmap_words_to_bytes(w.data(), n, exact.data());
+      CHECK(!memcmp(guarded.data(), exact.data(), nb));
+      const uint64_t fb = fold_classes(cls.data(), n, folded.data());
+      CHECK(fold_classes(cls.data(), n, folded_exact.data()) == fb && fold_classes(cls.data(), n, nullptr) == fb);
+      CHECK(!memcmp(folded.data(), folded_exact.data(), nb));
+      out += std::string(first ? "" : ", ") + "{\"n\": " + std::to_string(n) + ", \"bytes\": \"" +
+             hex(guarded.data(), nb + 2) + "\", \"fold\": \"" + hex(folded.data(), nb + 2) +
+             "\", \"first_bad\": " + std::to_string(fb) + "}";
+      first = false;
+    }
+  out += "], \"or_bits\": [";
+  first = true;
+  for (size_t n : sizes)
+    for (size_t s = 0; s < 8; s++) {
+      const size_t pos = 8 * (n % 3) + s, nb = (n + 7) / 8, cover = (pos + n + 7) / 8;
+      std::vector<uint8_t> src(nb), dst(cover + 1, 0);  // one guard byte behind the last byte a bit can reach
+      for (size_t j = 0; j < nb; j++) src[j] = (uint8_t)(37 * j + 11 * n + 0x5B);
+      or_bits_at(dst.data(), src.data(), n, pos);
+      out += std::string(first ? "" : ", ") + "\"" + hex(dst.data(), cover + 1) + "\"";
+      first = false;
+    }
+  out += "], \"select\": [";
+  struct Sel {
+    std::vector<uint8_t> cls;
+    std::vector<uint32_t> index;
+    size_t lo, hi, t, n;
+  };
+  const std::vector<Sel> sels = {
+      {{0, 0, 0, 0}, {3, 3, 5, 6}, 0, 4, 3, 10},        // a duplicate counts toward t, then collapses
+      {{0, 0, 0, 0}, {1, 12, 2, 4}, 0, 4, 3, 10},       // an index >= n is dropped
+      {{0, 7, 0, 5, 0}, {0, 1, 2, 3, 4}, 0, 5, 3, 10},  // invalid shares are skipped
+      {{0, 0, 0}, {9, 8, 7}, 0, 3, 3, 10},              // exactly t distinct
+      {{0, 0}, {9, 8}, 0, 2, 3, 10},                    // t - 1 distinct
+      {{0, 0, 0, 0, 0, 6, 0, 0, 0, 0}, {0, 1, 2, 3, 4, 5, 6, 7, 8, 9}, 4, 9, 3, 10},  // [lo, hi) of a larger round
+  };
+  for (size_t k = 0; k < sels.size(); k++) {
+    std::vector<uint32_t> sel, idx;
+    const bool ok = select_shares(sels[k].cls, sels[k].index, sels[k].lo, sels[k].hi, sels[k].t, sels[k].n, sel, idx);
+    out += std::string(k ? ", " : "") + "{\"ok\": " + (ok ? "true" : "false") + ", \"sel\": " + list_of(sel) +
+           ", \"idx\": " + list_of(idx) + "}";
+  }
+  out += "], \"share_indices\": [";
+  {
+    std::vector<uint8_t> parts(3 * 98, 0x11);
+    const uint32_t want[3] = {0, 0x0102, 0xffff};
+    for (size_t i = 0; i < 3; i++) parts[i * 98] = (uint8_t)(want[i] >> 8), parts[i * 98 + 1] = (uint8_t)want[i];
+    std::vector<uint32_t> index, none;
+    share_indices(parts.data(), 98, 3, index);
+    std::vector<uint8_t> tiny(3, 0x22);
+    share_indices(tiny.data(), 1, 3, none);
+    out += list_of(index) + ", " + list_of(none);
+  }
+  out += "], \"lagrange\": [";
+  std::vector<std::vector<uint32_t>> sets = {{0}, {0, 1}, {5, 2, 9}, {}};
+  for (uint32_t i = 0; i < 33; i++) sets[3].push_back((i * 37 + 11) % 1000);
+  for (size_t k = 0; k < sets.size(); k++) {
+    const size_t t = sets[k].size();
+    std::vector<uint32_t> lam(t * 8);
+    host_lagrange(sets[k].data(), t, lam.data());
+    out += std::string(k ? ", " : "") + "[";
+    for (size_t i = 0; i < t; i++) {
+      uint8_t be[32];  // big-endian, as an integer reads
+      for (int wd = 0; wd < 8; wd++)
+        for (int b = 0; b < 4; b++) be[31 - (4 * wd + b)] = (uint8_t)(lam[i * 8 + wd] >> (8 * b));
+      out += std::string(i ? ", " : "") + "\"" + hex(be, 32) + "\"";
+    }
+    out += "]";
+  }
+  out += "], \"scalar_mod_r\": [";
+  {
+    // 0, r - 1, r, r + 1, 2^256 - 1 (big-endian)
+    const char* in[5] = {"0000000000000000000000000000000000000000000000000000000000000000",
+                         "73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000000",
+                         "73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001",
+                         "73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000002",
+                         "ffffffffffffffffffffffffffffffffffffffffffffffffffffffffffffffff"};
+    for (int k = 0; k < 5; k++) {
+      std::vector<uint8_t> be(32);
+      for (int i = 0; i < 32; i++) be[i] = (uint8_t)strtoul(std::string(in[k] + 2 * i, 2).c_str(), nullptr, 16);
+      uint32_t wd[8];
+      scalar_mod_r(be.data(), wd);
+      uint8_t o[32];
+      for (int i = 0; i < 8; i++)
+        for (int b = 0; b < 4; b++) o[31 - (4 * i + b)] = (uint8_t)(wd[i] >> (8 * b));
+      out += std::string(k ? ", " : "") + "\"" + hex(o, 32) + "\"";
+    }
+  }
+  out += "], \"rlc_failing_items\": [";
+  {
+    struct Rlc {
+      size_t cnt, G;
+      std::vector<uint32_t> fail;
+    };
+    const std::vector<Rlc> cases = {{197, 64, {3}}, {197, 64, {0, 3}}, {128, 64, {1}}, {65, 8, {8}}};
+    for (size_t k = 0; k < cases.size(); k++)
+      out += (k ? ", " : "") +
+             std::to_string(rlc_failing_items(cases[k].cnt, cases[k].G, cases[k].fail.data(), cases[k].fail.size()));
+  }
+  out += "], \"svc_layout\": [";
+  {
+    const size_t cases[4][2] = {{1, 0}, {3, 32}, {7, 100}, {64, 2048}};
+    for (int k = 0; k < 4; k++) {
+      const SvcLayout l = svc_layout(cases[k][0], cases[k][1]);
+      out += std::string(k ? ", " : "") + "[" + std::to_string(l.o_len) + ", " + std::to_string(l.o_idx) + ", " +
+             std::to_string(l.o_sig) + ", " + std::to_string(l.o_msg) + ", " + std::to_string(l.total) + "]";
+    }
+  }
+  out += "]}}";
+  puts(out.c_str());
+  return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
   if (argc >= 2 && !strcmp(argv[1], "coalesce")) test_coalesce();
   else if (argc >= 3 && !strcmp(argv[1], "boltload")) test_boltload(argc - 2, argv + 2);
+  else if (argc >= 2 && !strcmp(argv[1], "hostlogic")) test_hostlogic();
   else {
-    fprintf(stderr, "usage: %s coalesce | boltload file.db...\n", argv[0]);
+    fprintf(stderr, "usage: %s coalesce | boltload file.db... | hostlogic\n", argv[0]);
     return 2;
   }
   if (fails) fprintf(stderr, "%d checks failed\n", fails);
