@@ -18,11 +18,11 @@ int ensure_workspace(blsv_ctx* c, size_t cnt) {
       if (e == hipSuccess) e = d.ensure(bytes);
     };
     need(c->H, want * blsk::H_WORDS * 4);
-    need(c->HQ, want * blsk::HQ_WORDS * 4);
+    need(c->HQ, kHqWords(want) * 4);  // with the final exponentiation's park (engine_ctx.h)
     need(c->S, want * blsk::S_WORDS * 4);
     need(c->F, want * blsk::F_WORDS * 4);
     need(c->FW, 3 * want * blsk::F_WORDS * 4);
-    // LN doubles as the final exponentiation's park
+    // (a timelock pass, which stages no lines, parks its final exponentiation in LN)
     need(c->LN, std::max(std::min(want, kLineSub) * blsk::MILLER_LINE_WORDS, blsk::FEXP_PARK_WORDS(want)) * 4);
     need(c->h_inf, want);
     need(c->s_inf, want);
@@ -124,6 +124,9 @@ int blsv_create(int device, blsv_ctx** out) {
     if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&c->fork_ev, hipEventDisableTiming);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&c->join_ev, hipEventDisableTiming);
+  int cus = 0;
+  if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
+  c->tail_q_dev = c->tail_q = size_t(64) * 4 * (size_t)std::max(cus, 0);
   if (e != hipSuccess) {
     fprintf(stderr, "blsv_create: %s\n", hipGetErrorString(e));
     blsv_destroy(c);  // releases whatever was created
@@ -146,10 +149,9 @@ void blsv_destroy(blsv_ctx* c) {
   if (c->fork_ev) (void)hipEventDestroy(c->fork_ev);
   if (c->join_ev) (void)hipEventDestroy(c->join_ev);
   (void)hipDeviceSynchronize();
-  for (auto& r : c->recs) {
-    (void)hipEventDestroy(r.a);
-    (void)hipEventDestroy(r.b);
-  }
+  for (auto& r : c->recs)
+    for (hipEvent_t e : {r.a, r.b, r.a2, r.b2})
+      if (e) (void)hipEventDestroy(e);
   for (auto e : c->event_pool) (void)hipEventDestroy(e);
   delete c;
 }
@@ -181,13 +183,19 @@ int blsv_profile_read(blsv_ctx* c, double* ms, uint64_t* launches, uint64_t* ite
     HIPCHK(c, hipEventSynchronize(r.b));
     float t = 0;
     HIPCHK(c, hipEventElapsedTime(&t, r.a, r.b));
+    if (r.a2 && r.b2) {  // a split pass's side span: summed, one launch
+      float t2 = 0;
+      HIPCHK(c, hipEventSynchronize(r.b2));
+      HIPCHK(c, hipEventElapsedTime(&t2, r.a2, r.b2));
+      t += t2;
+    }
     if (r.stage < nstages) {
       if (ms) ms[r.stage] += t;
       if (launches) launches[r.stage] += 1;
       if (items) items[r.stage] += r.items;
     }
-    c->event_pool.push_back(r.a);
-    c->event_pool.push_back(r.b);
+    for (hipEvent_t e : {r.a, r.b, r.a2, r.b2})
+      if (e) c->event_pool.push_back(e);
   }
   c->recs.clear();
   return ST_N;

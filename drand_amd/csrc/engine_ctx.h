@@ -18,8 +18,8 @@
 
 namespace blsv_detail {
 
-// Beacons per pipeline pass. The staging of one pass is kStagingBytesPerItem per item (~42.4 KB, 39 KB
-// of it the Miller line staging): ~43 GB of the 288 GB at the full 2^20 chunk. A context's chunk is
+// Beacons per pipeline pass. The staging of one pass is at most kStagingBytesPerItem per item (~42.4 KB,
+// 39 KB of it the Miller line staging): ~43 GB of the 288 GB at the full 2^20 chunk. A context's chunk is
 // capped by blsv_set_chunk / BLSV_CHUNK and halves itself when an allocation fails (ensure_workspace).
 constexpr size_t kMaxChunk = size_t(1) << 20;
 constexpr size_t kMinChunk = size_t(1) << 14;  // the OOM fallback stops here
@@ -28,8 +28,31 @@ constexpr size_t kMinChunk = size_t(1) << 14;  // the OOM fallback stops here
 // eight of each, so one wave tail instead of eight).
 constexpr size_t kLineSub = kMaxChunk;
 constexpr size_t kPkTable = 4096;  // member indices with a precomputed PK_i (drand groups are far smaller)
+// HQ also holds the final exponentiation's park (below): 64 lanes of 48 words per 21 items, 146.3 words
+// per item against HQ_WORDS = 144, plus one wave for the second range of a split pass
+constexpr size_t kFexpParkWords(size_t items) { return blsk::FEXP_PARK_WORDS(items) + 48 * 64; }
+constexpr size_t kHqWords(size_t items) { return std::max(items * blsk::HQ_WORDS, kFexpParkWords(items)); }
 constexpr size_t kStagingBytesPerItem =
-    4 * (blsk::H_WORDS + blsk::HQ_WORDS + blsk::S_WORDS + 4 * blsk::F_WORDS + blsk::MILLER_LINE_WORDS) + 3;
+    4 * (blsk::H_WORDS + blsk::HQ_WORDS + 3 + blsk::S_WORDS + 4 * blsk::F_WORDS + blsk::MILLER_LINE_WORDS) + 3;
+static_assert(kHqWords(kMaxChunk) <= (blsk::HQ_WORDS + 3) * kMaxChunk, "kStagingBytesPerItem: HQ with the park");
+// Which stage owns which staging buffer of a pass, and when (all on the launch stream unless said):
+//   H, h_inf   hash writes; the Miller lines pass reads (the randomized tail's sums and gather too)
+//   HQ         hash, between its kernels; then free until the final exponentiation parks its 3-lane
+//              products in it: the main range in the first FEXP_PARK_WORDS(main) words, the remainder of
+//              a split pass behind them. A timelock pass captures its values in HQ and parks in LN.
+//   S, s_inf   decompression (side stream, joined before the Miller stage) writes; the lines pass reads
+//   cls        decompression writes; the lines pass adds REJ_NOT_IN_SUBGROUP, the final exponentiation
+//              REJ_PAIRING, each to its own items' bytes; finish reads
+//   LN         the lines pass writes; the f pass reads. Nothing else writes LN while a pass is in flight
+//              (it used to double as the park: a split pass's remainder still reads its lines while
+//              the main range is in its final exponentiation)
+//   F          the f pass writes; the final exponentiation consumes and reuses as scratch
+//   FW         the 3-lane f pass parks in it; then the final exponentiation's G, B, C
+// A split pass (hostlogic.h tail_split_main, verify.cpp pairing_check): after the f pass of the main
+// range [0, main) the side stream runs the f pass and the final exponentiation of [main, cnt) beside the
+// main range's final exponentiation on the launch stream. The two touch disjoint columns of F, FW and
+// cls and disjoint park areas; the remainder alone reads LN; the launch stream joins the side stream
+// before finish, so before the next pass's head writes S, H, HQ and cls.
 // Every SoA staging object is reached through 32-bit buffer resources (soa.h): num_records is
 // min(bytes, 2^31 - 1) and offsets are uint32. The largest object resource (soa_obj_rsrc over 12 Fp
 // slots, 576 bytes per item) and the largest VGPR offset ((11 * 12 * n + i) * 4) must fit at the
@@ -115,10 +138,14 @@ enum Stage {
   ST_TLOCK = 7,  // timelock opening: sigma's preparation and the f pass (its final exponentiation is ST_FEXP)
   ST_N = 8
 };
+// One record is one launch of a stage over `items` items. A split pass's Miller and final-exponentiation
+// records carry a second span (a2, b2: the remainder on the side stream); blsv_profile_read adds the two,
+// so time in which the spans overlap counts twice and a pass's stage times may exceed its wall time.
 struct ProfRec {
   int stage;
   size_t items;
   hipEvent_t a, b;
+  hipEvent_t a2 = nullptr, b2 = nullptr;
 };
 
 // Cutover between the latency path (one workgroup per item, k_lat.hip) and the batch pipeline: a batch
@@ -194,6 +221,9 @@ struct blsv_ctx {
   size_t chunk = chunk_env();                      // items per pipeline pass (blsv_set_chunk)
   size_t lat_max = std::min(lat_max_env(), chunk);  // latency-path cutover, never above the chunk
   uint64_t oom_halvings = 0;                        // times ensure_workspace halved the chunk
+  // one round of the single-lane Miller f pass (64 lanes x 4 SIMDs x the device's compute units, read
+  // in blsv_create), and the round a pass is split by (hostlogic.h tail_split_main; blsv_test_tail_split)
+  size_t tail_q_dev = 0, tail_q = 0;
   std::vector<ProfRec> recs;
   std::vector<hipEvent_t> event_pool;
   hipStream_t stream = nullptr;

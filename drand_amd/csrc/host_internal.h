@@ -85,11 +85,16 @@ inline void lat_uploaded(blsv_ctx* c, const SigSrc& sig, size_t cnt, const PkSel
   blsk::launch_lat_messages(c->in_msgs.as<uint8_t>(), c->in_off.as<uint64_t>(), c->in_len.as<uint32_t>(), sig.d,
                             sig.stride, sig.offset, cnt, pk.tab, pk.inf, pk.idx, cls, S, s_inf, st);
 }
-// the final exponentiation of the cnt values in F (W = FW; its kept squares and 3-lane products park
-// in LN, free after the Miller stage); out (optional) captures the exponentiated values
-inline void final_exp(blsv_ctx* c, size_t cnt, uint8_t* cls, hipStream_t st, uint32_t* out = nullptr) {
+// the final exponentiation of the values [base, base + m) of the cnt in F (W = FW); its 3-lane products
+// park in HQ, free after the hash stage: the range from 0 first, a range from base behind the park of
+// the base items before it (engine_ctx.h kHqWords holds both); out (optional) captures the values
+inline void final_exp(blsv_ctx* c, size_t cnt, size_t base, size_t m, uint8_t* cls, hipStream_t st,
+                      uint32_t* out = nullptr) {
   const Staging w = staging(c);
-  blsk::launch_final_exp(w.F, w.FW, cnt, cls, st, w.LN, out);
+  blsk::launch_final_exp(w.F, w.FW, cnt, base, m, cls, st, w.HQ + (base ? blsk::FEXP_PARK_WORDS(base) : 0), out);
+}
+inline void final_exp(blsv_ctx* c, size_t cnt, uint8_t* cls, hipStream_t st, uint32_t* out = nullptr) {
+  final_exp(c, cnt, 0, cnt, cls, st, out);
 }
 
 // ---- verify.cpp: the pass loop

@@ -252,6 +252,15 @@ inline size_t rlc_failing_items(size_t cnt, size_t G, const uint32_t* fail, size
   return nf * G - (fail[nf - 1] == ng - 1 ? ng * G - cnt : 0);
 }
 
+// The main part of a pass of cnt items whose Miller f pass runs in rounds of q items (one single-lane
+// wave on every SIMD): the whole rounds, when a partial last round follows at least one of them. The
+// remainder [main, cnt) then runs its f pass beside the main part's final exponentiation (verify.cpp
+// pairing_check). cnt itself means no split: q == 0, a pass of at most one round, or whole rounds only.
+inline size_t tail_split_main(size_t cnt, size_t q) {
+  if (q == 0 || cnt <= q || cnt % q == 0) return cnt;
+  return cnt - cnt % q;
+}
+
 // svc_verify_mixed's packed upload of n items with mbytes message bytes:
 // off[n + 1] | lens[n] | idx[n] | sigs[n][96] | message bytes (8-byte aligned parts)
 struct SvcLayout {

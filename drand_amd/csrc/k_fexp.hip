@@ -6,10 +6,12 @@
 
 namespace blsk {
 
-BLS_KERNEL(BLS_WPE_FEXP) k_fexp_easy(const uint32_t* F, size_t cnt, const uint8_t* cls, uint32_t* G) {
+// Every kernel here works on a range of m items of a pass whose SoA staging has stride n: F, G, cls (and
+// X, C, OUT below) point at the range's first column, so item i of the range is column i of stride n.
+BLS_KERNEL(BLS_WPE_FEXP) k_fexp_easy(const uint32_t* F, size_t n, size_t m, const uint8_t* cls, uint32_t* G) {
   size_t i = (size_t)blockIdx.x * TPB + threadIdx.x;
-  if (i >= cnt || cls[i] != REJ_OK) return;
-  st_fp12(G, cnt, i, fexp_easy(ld_fp12(F, cnt, i)));
+  if (i >= m || cls[i] != REJ_OK) return;
+  st_fp12(G, n, i, fexp_easy(ld_fp12(F, n, i)));
 }
 
 // ------------------------------------------------------------------ 3-lane hard part (tri.h)
@@ -45,22 +47,22 @@ DI fp4 tri_pow_x_abs(const tri_lane& t, LoadX lx, const TriPark& pk) {
 // Karabina compressed squaring chain on 2 lanes + batch decompression (162.8 ms against 160.9) and
 // the A0 / (A1, A2) halves of the squaring as two one-lane kernels (169.6 ms); git history holds them.
 template <int MODE>
-BLS_KERNEL(BLS_WPE_FEXP_TRI) k_fexp_tri(const uint32_t* X, const uint32_t* C, const uint32_t* G, size_t cnt,
+BLS_KERNEL(BLS_WPE_FEXP_TRI) k_fexp_tri(const uint32_t* X, const uint32_t* C, const uint32_t* G, size_t n, size_t m,
                                         uint8_t* cls, uint32_t* OUT, uint32_t* park) {
   const tri_lane t = tri_lane_id();
 #if BLS_CSQR_LIN
   kp_lds_init<11>();
 #endif
   const size_t ir = (size_t)blockIdx.x * TRI_GROUPS + t.group;
-  const bool in_range = t.group < TRI_GROUPS && ir < cnt;
-  const size_t i0 = in_range ? ir : cnt - 1;  // dummy lanes compute on a real row, never store
+  const bool in_range = t.group < TRI_GROUPS && ir < m;
+  const size_t i0 = in_range ? ir : m - 1;  // dummy lanes compute on a real row, never store
   const bool live = in_range && cls[i0] == REJ_OK;
   const TriPark pk = {park, (size_t)gridDim.x * TPB, (size_t)blockIdx.x * TPB + t.lane};
   // every lane stays active to the end (ds_bpermute reads its partners' registers)
   auto at = [&](const uint32_t* B) {
     size_t j = i0;
     asm volatile("" : "+v"(j));  // re-read at each use, never hoisted (a hoisted Fp12 pins its registers)
-    return tri_load(B, cnt, j, t.role);
+    return tri_load(B, n, j, t.role);
   };
   fp4 r = tri_conj(t, tri_pow_x_abs(t, [&]() { return at(X); }, pk));
   if (MODE == 0 || MODE == 1) r = tri_mul_lp(t, r, tri_conj(t, at(X)), pk.p, pk.n, pk.i);
@@ -72,7 +74,7 @@ BLS_KERNEL(BLS_WPE_FEXP_TRI) k_fexp_tri(const uint32_t* X, const uint32_t* C, co
     r = tri_mul_lp(t, r, at(G), pk.p, pk.n, pk.i);
   }
   if (MODE < 4 || OUT) {  // MODE 4 with OUT: the final value too (blsv_test_final_exp)
-    if (live) tri_store(OUT, cnt, i0, t.role, r);
+    if (live) tri_store(OUT, n, i0, t.role, r);
   }
   if (MODE == 4) {
     const bool one = tri_is_one(t, r);
@@ -81,23 +83,28 @@ BLS_KERNEL(BLS_WPE_FEXP_TRI) k_fexp_tri(const uint32_t* X, const uint32_t* C, co
 }
 
 // ------------------------------------------------------------------ launchers
-// F (Miller output) is consumed by the easy part and then reused as scratch; W holds 3 more Fp12
-// staging slots of cnt entries each (G, B, C). park: FEXP_PARK_WORDS(cnt) words for the 3-lane
-// products' parked partial results.
-void launch_final_exp(uint32_t* F, uint32_t* W, size_t cnt, uint8_t* cls, hipStream_t st, uint32_t* park,
-                      uint32_t* out) {
-  if (!cnt) return;
-  uint32_t* G = W;
-  uint32_t* B = W + cnt * F_WORDS;
-  uint32_t* C = W + 2 * cnt * F_WORDS;
-  const dim3 grid(grid_for(cnt)), blk(TPB);
-  hipLaunchKernelGGL(k_fexp_easy, grid, blk, 0, st, F, cnt, cls, G);
-  const dim3 tgrid((unsigned)((cnt + TRI_GROUPS - 1) / TRI_GROUPS));
-  hipLaunchKernelGGL(k_fexp_tri<0>, tgrid, blk, 0, st, G, nullptr, nullptr, cnt, cls, F, park);    // a -> F
-  hipLaunchKernelGGL(k_fexp_tri<1>, tgrid, blk, 0, st, F, nullptr, nullptr, cnt, cls, B, park);    // b -> B
-  hipLaunchKernelGGL(k_fexp_tri<2>, tgrid, blk, 0, st, B, nullptr, nullptr, cnt, cls, C, park);    // c -> C
-  hipLaunchKernelGGL(k_fexp_tri<3>, tgrid, blk, 0, st, C, nullptr, nullptr, cnt, cls, F, park);    // t -> F
-  hipLaunchKernelGGL(k_fexp_tri<4>, tgrid, blk, 0, st, F, C, G, cnt, cls, out, park);
+// The m items [base, base + m) of a pass whose staging has stride n. F (Miller output) is consumed by
+// the easy part and then reused as scratch; W holds 3 more Fp12 staging slots of n entries each (G, B,
+// C). Only the range's columns of F, W, cls and out are touched, so two disjoint ranges of one pass may
+// run side by side on two streams, each with a park area of its own. park: FEXP_PARK_WORDS(m) words
+// for the 3-lane products' parked partial results.
+void launch_final_exp(uint32_t* F, uint32_t* W, size_t n, size_t base, size_t m, uint8_t* cls, hipStream_t st,
+                      uint32_t* park, uint32_t* out) {
+  if (!m) return;
+  F += base;
+  cls += base;
+  if (out) out += base;
+  uint32_t* G = W + base;
+  uint32_t* B = G + n * F_WORDS;
+  uint32_t* C = G + 2 * n * F_WORDS;
+  const dim3 grid(grid_for(m)), blk(TPB);
+  hipLaunchKernelGGL(k_fexp_easy, grid, blk, 0, st, F, n, m, cls, G);
+  const dim3 tgrid((unsigned)((m + TRI_GROUPS - 1) / TRI_GROUPS));
+  hipLaunchKernelGGL(k_fexp_tri<0>, tgrid, blk, 0, st, G, nullptr, nullptr, n, m, cls, F, park);    // a -> F
+  hipLaunchKernelGGL(k_fexp_tri<1>, tgrid, blk, 0, st, F, nullptr, nullptr, n, m, cls, B, park);    // b -> B
+  hipLaunchKernelGGL(k_fexp_tri<2>, tgrid, blk, 0, st, B, nullptr, nullptr, n, m, cls, C, park);    // c -> C
+  hipLaunchKernelGGL(k_fexp_tri<3>, tgrid, blk, 0, st, C, nullptr, nullptr, n, m, cls, F, park);    // t -> F
+  hipLaunchKernelGGL(k_fexp_tri<4>, tgrid, blk, 0, st, F, C, G, n, m, cls, out, park);
 }
 
 }  // namespace blsk

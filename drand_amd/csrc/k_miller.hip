@@ -349,29 +349,52 @@ bool launch_test_op_mf(int op, const uint32_t* in, size_t cnt, uint32_t* out, hi
 }
 
 // ------------------------------------------------------------------ launchers
-// The line staging (MILLER_LINE_WORDS per beacon) holds `sub` beacons; the chunk runs in sub-chunks
-// (one when sub >= cnt, which is what the host does: every sub-chunk adds a wave tail to both passes).
+// The line staging (MILLER_LINE_WORDS per beacon) holds `sub` beacons: item g of the pass has its lines
+// at LN index g % sub.
+// The lines pass of the m items [base, base + m) of a pass of cnt items, base a multiple of sub and
+// m <= sub.
+void launch_miller_lines(const uint32_t* pk_tab, const uint8_t* pk_inf, const uint32_t* pk_idx, const uint32_t* H,
+                         const uint8_t* h_inf, const uint32_t* S, const uint8_t* s_inf, uint8_t* cls, size_t cnt,
+                         size_t base, size_t m, uint32_t* LN, size_t sub, bool check_subgroup, hipStream_t st) {
+  if (!m) return;
+  if (check_subgroup)
+    hipLaunchKernelGGL(k_miller_lines<true>, dim3(2 * grid_for(m)), dim3(TPB), 0, st, pk_tab, pk_inf, pk_idx, H, h_inf,
+                       S, s_inf, cls, cnt, base, m, sub, LN);
+  else
+    hipLaunchKernelGGL(k_miller_lines<false>, dim3(2 * grid_for(m)), dim3(TPB), 0, st, pk_tab, pk_inf, pk_idx, H,
+                       h_inf, S, s_inf, (const uint8_t*)cls, cnt, base, m, sub, LN);
+}
+
+// The f pass of the m items [base, base + m), all inside one sub-chunk of the line staging: the kernels
+// index the lines from 0, so LN moves to the range's first column (base % sub; the slot resources of
+// soa.h then end that many words later, still inside the next slot or the buffer's own last one, and
+// no lane reaches past column m).
+void launch_miller_f(const uint32_t* LN, size_t sub, const uint8_t* cls, size_t cnt, size_t base, size_t m,
+                     uint32_t* F, uint32_t* park, bool single_lane, hipStream_t st) {
+  if (!m) return;
+  LN += base % sub;
+  // Below one full wave round of the single-lane pass (1 wave/SIMD x 1024 SIMDs x 64 lanes) the GPU is
+  // not full and latency decides: the 3-lane pass runs 27.6 k instructions per lane-step against
+  // 73.7 k. At full occupancy the single-lane pass has the higher throughput (profiles/r02_*), and so
+  // it has for a small range that shares the GPU with other work (single_lane).
+  if (m <= kMillerTriMax && !single_lane) {
+    hipLaunchKernelGGL(k_miller_f_tri, dim3((unsigned)((m + TRI_GROUPS - 1) / TRI_GROUPS)), dim3(TPB), 0, st, LN, cls,
+                       cnt, base, m, sub, F, park);
+  } else {
+    hipLaunchKernelGGL(k_miller_f, dim3(grid_for(m)), dim3(TPB), 0, st, LN, cls, cnt, base, m, sub, F);
+  }
+}
+
+// Both passes over a whole pass, in sub-chunks of the line staging (one when sub >= cnt, which is what
+// the host does: every sub-chunk adds a wave tail to both passes).
 void launch_miller(const uint32_t* pk_tab, const uint8_t* pk_inf, const uint32_t* pk_idx, const uint32_t* H,
                    const uint8_t* h_inf, const uint32_t* S, const uint8_t* s_inf, uint8_t* cls, size_t cnt,
                    uint32_t* F, uint32_t* LN, size_t sub, uint32_t* park, bool check_subgroup, hipStream_t st) {
   if (!cnt) return;
   for (size_t b = 0; b < cnt; b += sub) {
     const size_t m = cnt - b < sub ? cnt - b : sub;
-    if (check_subgroup)
-      hipLaunchKernelGGL(k_miller_lines<true>, dim3(2 * grid_for(m)), dim3(TPB), 0, st, pk_tab, pk_inf, pk_idx, H,
-                         h_inf, S, s_inf, cls, cnt, b, m, sub, LN);
-    else
-      hipLaunchKernelGGL(k_miller_lines<false>, dim3(2 * grid_for(m)), dim3(TPB), 0, st, pk_tab, pk_inf, pk_idx, H,
-                         h_inf, S, s_inf, (const uint8_t*)cls, cnt, b, m, sub, LN);
-    // Below one full wave round of the single-lane pass (1 wave/SIMD x 1024 SIMDs x 64 lanes) the GPU is
-    // not full and latency decides: the 3-lane pass runs 27.6 k instructions per lane-step against
-    // 73.7 k. At full occupancy the single-lane pass has the higher throughput (profiles/r02_*).
-    if (m <= kMillerTriMax) {
-      hipLaunchKernelGGL(k_miller_f_tri, dim3((unsigned)((m + TRI_GROUPS - 1) / TRI_GROUPS)), dim3(TPB), 0, st, LN,
-                         cls, cnt, b, m, sub, F, park);
-    } else {
-      hipLaunchKernelGGL(k_miller_f, dim3(grid_for(m)), dim3(TPB), 0, st, LN, cls, cnt, b, m, sub, F);
-    }
+    launch_miller_lines(pk_tab, pk_inf, pk_idx, H, h_inf, S, s_inf, cls, cnt, b, m, LN, sub, check_subgroup, st);
+    launch_miller_f(LN, sub, cls, cnt, b, m, F, park, false, st);
   }
 }
 

@@ -57,14 +57,26 @@ constexpr int MILLER_LINE_WORDS = 68 * 2 * 6 * 12;
 void launch_miller(const uint32_t* pk_tab, const uint8_t* pk_inf, const uint32_t* pk_idx, const uint32_t* H,
                    const uint8_t* h_inf, const uint32_t* S, const uint8_t* s_inf, uint8_t* cls, size_t cnt,
                    uint32_t* F, uint32_t* LN, size_t sub, uint32_t* park, bool check_subgroup, hipStream_t st);
+// launch_miller's two halves, for a caller that sequences them itself (cnt = the pass, the stride of
+// H / S / F / cls): the lines pass of the items [base, base + m) (base a multiple of sub, m <= sub),
+// and the f pass of a range [base, base + m) inside one sub-chunk whose lines are staged. single_lane
+// forces k_miller_f whatever m is: the form with the least SIMD time, for a small range that runs
+// beside other work instead of alone.
+void launch_miller_lines(const uint32_t* pk_tab, const uint8_t* pk_inf, const uint32_t* pk_idx, const uint32_t* H,
+                         const uint8_t* h_inf, const uint32_t* S, const uint8_t* s_inf, uint8_t* cls, size_t cnt,
+                         size_t base, size_t m, uint32_t* LN, size_t sub, bool check_subgroup, hipStream_t st);
+void launch_miller_f(const uint32_t* LN, size_t sub, const uint8_t* cls, size_t cnt, size_t base, size_t m,
+                     uint32_t* F, uint32_t* park, bool single_lane, hipStream_t st);
 // park: TRI_PARK_WORDS(sub) words of scratch for the 3-lane f pass (48 words per lane, 21 items per wave)
 constexpr size_t TRI_PARK_WORDS(size_t items) { return 48 * 64 * ((items + 20) / 21); }
-// F is clobbered; W = 3 * cnt * F_WORDS words of staging; out (optional, test hook): the
-// exponentiated values (SoA, cnt * F_WORDS words)
-// park: FEXP_PARK_WORDS(cnt) words of scratch for the 3-lane products' parked partial results
+// The final exponentiation of the m items [base, base + m) of a pass whose staging has stride n: their
+// columns of F are clobbered; W = 3 * n * F_WORDS words of staging (the range's columns are used); out
+// (optional: test hook, timelock): the exponentiated values (SoA of stride n, the range's columns).
+// park: FEXP_PARK_WORDS(m) words of scratch for the 3-lane products' parked partial results; ranges
+// that run side by side need disjoint park areas.
 constexpr size_t FEXP_PARK_WORDS(size_t items) { return TRI_PARK_WORDS(items); }
-void launch_final_exp(uint32_t* F, uint32_t* W, size_t cnt, uint8_t* cls, hipStream_t st, uint32_t* park,
-                      uint32_t* out = nullptr);
+void launch_final_exp(uint32_t* F, uint32_t* W, size_t n, size_t base, size_t m, uint8_t* cls, hipStream_t st,
+                      uint32_t* park, uint32_t* out = nullptr);
 // bitmap bit (base+i) = (cls[i] == 0); bitmap must cover whole 64-bit words;
 // first_bad = label0 + min rejected index (label0 = first_round -> ROUND numbers)
 void launch_finish(const uint8_t* cls, size_t base, size_t cnt, uint64_t* bitmap, unsigned long long* first_bad,

@@ -80,6 +80,12 @@ int blsv_test_spec_stats(blsv_ctx* c, uint64_t* hits, uint64_t* misses) {
   return BLSV_OK;
 }
 
+int blsv_test_tail_split(blsv_ctx* c, size_t q) {
+  if (!c) return BLSV_EINVAL;
+  c->tail_q = q == SIZE_MAX ? c->tail_q_dev : q;
+  return BLSV_OK;
+}
+
 int blsv_test_generic_chains(blsv_ctx* c, int on) {
   if (!c) return BLSV_EINVAL;
   blsk::g_generic_chains_all = on != 0;
@@ -162,8 +168,11 @@ int blsv_test_final_exp(blsv_ctx* c, const uint32_t* f, size_t n, uint32_t* out_
   HIPCHK(c, hipMemsetAsync(w.cls, 0, n, c->stream));
   blsk::launch_test_pack_fp12(din.as<uint32_t>(), n, w.F, c->stream);
   blsk::launch_test_final_exp_ref(w.F, n, dref.as<uint32_t>(), c->stream);
-  // the production stage (clobbers F), its final value captured into dout
-  final_exp(c, n, w.cls, c->stream, dout.as<uint32_t>());
+  // the production stage (clobbers F), its final value captured into dout: whole, or as the two ranges
+  // of the context's split rule (blsv_test_tail_split), one after the other with their own park areas
+  const size_t mn = tail_split_main(n, c->tail_q);
+  final_exp(c, n, 0, mn, w.cls, c->stream, dout.as<uint32_t>());
+  final_exp(c, n, mn, n - mn, w.cls, c->stream, dout.as<uint32_t>());
   blsk::launch_test_unpack_fp12(dout.as<uint32_t>(), n, din.as<uint32_t>(), c->stream);
   HIPCHK(c, hipMemcpyAsync(out_pipeline, din.p, n * 576, hipMemcpyDeviceToHost, c->stream));
   blsk::launch_test_unpack_fp12(dref.as<uint32_t>(), n, dout.as<uint32_t>(), c->stream);

@@ -58,7 +58,8 @@ static int tlock_pass(blsv_ctx* c, const uint8_t* d_us, size_t cnt, uint8_t* d_o
   }
   {
     StageTimer tm(c, ST_FEXP, cnt, st);
-    final_exp(c, cnt, w.cls, st, w.HQ);
+    // the values are captured in HQ, so the park stays in LN (a timelock pass stages no lines)
+    blsk::launch_final_exp(w.F, w.FW, cnt, 0, cnt, w.cls, st, w.LN, w.HQ);
   }
   blsk::launch_tlock_encode(w.HQ, ucls, cnt, d_out, st);
   if (d_cls_out) HIPCHK(c, hipMemcpyAsync(d_cls_out, ucls, cnt, hipMemcpyDeviceToDevice, st));

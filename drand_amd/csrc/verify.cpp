@@ -59,17 +59,89 @@ int run_head(blsv_ctx* c, const SigSrc& sig, size_t base, size_t cnt, const Tail
   return BLSV_OK;
 }
 
-// Miller + final exponentiation of cnt staged items into their class bytes (F, FW, LN are the pass's)
-static void pairing_check(blsv_ctx* c, const PkSel& pk, const uint32_t* H, const uint8_t* h_inf, const uint32_t* S,
-                          const uint8_t* s_inf, uint8_t* cls, size_t cnt, bool check_subgroup, hipStream_t st) {
-  const Staging w = staging(c);
-  {
-    StageTimer tm(c, ST_MILLER, cnt, st);
-    blsk::launch_miller(pk.tab, pk.inf, pk.idx, H, h_inf, S, s_inf, cls, cnt, w.F, w.LN, std::min(cnt, kLineSub), w.FW,
-                        check_subgroup, st);
+// Drains the side stream when a split pass returns before the launch stream has joined it (an error
+// between the fork and the join): nothing of the pass may still run when the caller sees the error.
+struct SplitDrain {
+  blsv_ctx* c;
+  bool armed = false;
+  ~SplitDrain() {
+    if (armed) (void)hipStreamSynchronize(c->side);
   }
-  StageTimer tm(c, ST_FEXP, cnt, st);
-  final_exp(c, cnt, cls, st);
+};
+
+// Miller + final exponentiation of cnt staged items into their class bytes (F, FW, LN, HQ are the pass's).
+// The single-lane f pass runs one wave per SIMD, so a pass of r = cnt / tail_q rounds keeps only the
+// fraction r - floor(r) of the GPU busy for the whole of its last round. A pass with such a partial
+// last round (hostlogic.h tail_split_main) is split after the lines pass: the launch stream runs the f
+// pass and the final exponentiation of the whole rounds [0, main), the side stream (idle since the
+// head) the single-lane f pass and the final exponentiation of [main, cnt) once f(main) is done, so the
+// remainder's waves share the GPU with the main range's final exponentiation instead of running alone.
+// The stages are element-wise; engine_ctx.h says which columns and park areas each range owns. The
+// launch stream joins the side stream before it returns to the caller's finish. BLSV_SERIAL_STAGES=1
+// keeps every pass whole, like the head.
+// One profile record per stage and pass either way; a split pass's records carry both spans.
+static int pairing_check(blsv_ctx* c, const PkSel& pk, const uint32_t* H, const uint8_t* h_inf, const uint32_t* S,
+                         const uint8_t* s_inf, uint8_t* cls, size_t cnt, bool check_subgroup, hipStream_t st) {
+  const Staging w = staging(c);
+  const size_t mn = serial_stages() || cnt > kLineSub ? cnt : tail_split_main(cnt, c->tail_q);
+  if (mn == cnt) {
+    {
+      StageTimer tm(c, ST_MILLER, cnt, st);
+      blsk::launch_miller(pk.tab, pk.inf, pk.idx, H, h_inf, S, s_inf, cls, cnt, w.F, w.LN, std::min(cnt, kLineSub),
+                          w.FW, check_subgroup, st);
+    }
+    StageTimer tm(c, ST_FEXP, cnt, st);
+    final_exp(c, cnt, cls, st);
+    return BLSV_OK;
+  }
+  auto mark = [&](hipStream_t s) {
+    hipEvent_t e = c->prof ? take_event(c) : nullptr;
+    if (e) (void)hipEventRecord(e, s);
+    return e;
+  };
+  auto keep = [&](ProfRec r) {
+    if (!c->prof) return;
+    if (!r.a2 || !r.b2) {
+      for (hipEvent_t e : {r.a2, r.b2})
+        if (e) c->event_pool.push_back(e);
+      r.a2 = r.b2 = nullptr;
+    }
+    if (r.a && r.b) {
+      c->recs.push_back(r);
+    } else {
+      for (hipEvent_t e : {r.a, r.b, r.a2, r.b2})
+        if (e) c->event_pool.push_back(e);
+    }
+  };
+  ProfRec rm{ST_MILLER, cnt, nullptr, nullptr}, rf{ST_FEXP, cnt, nullptr, nullptr};
+  SplitDrain drain{c};
+  const size_t rem = cnt - mn;  // [0, mn) main range, [mn, cnt) remainder
+  rm.a = mark(st);
+  blsk::launch_miller_lines(pk.tab, pk.inf, pk.idx, H, h_inf, S, s_inf, cls, cnt, 0, cnt, w.LN, cnt, check_subgroup, st);
+  blsk::launch_miller_f(w.LN, cnt, cls, cnt, 0, mn, w.F, w.FW, false, st);
+  rm.b = mark(st);
+  int rc = BLSV_OK;
+  auto chk = [&](hipError_t e, const char* what) {
+    if (e != hipSuccess && rc == BLSV_OK) rc = fail(c, BLSV_EHIP, "%s: %s", what, hipGetErrorString(e));
+    return e == hipSuccess;
+  };
+  if (chk(hipEventRecord(c->fork_ev, st), "split fork") && chk(hipStreamWaitEvent(c->side, c->fork_ev, 0), "split fork")) {
+    drain.armed = true;
+    rm.a2 = mark(c->side);
+    blsk::launch_miller_f(w.LN, cnt, cls, cnt, mn, rem, w.F, nullptr, true, c->side);
+    rm.b2 = mark(c->side);
+    rf.a2 = mark(c->side);
+    final_exp(c, cnt, mn, rem, cls, c->side);
+    rf.b2 = mark(c->side);
+    rf.a = mark(st);
+    final_exp(c, cnt, 0, mn, cls, st);
+    rf.b = mark(st);
+    if (chk(hipEventRecord(c->join_ev, c->side), "split join") && chk(hipStreamWaitEvent(st, c->join_ev, 0), "split join"))
+      drain.armed = false;
+  }
+  keep(rm);
+  keep(rf);
+  return rc;
 }
 
 // the last stage of either tail: the pass's class bytes into the call's outputs
@@ -87,8 +159,8 @@ static int finish_pass(blsv_ctx* c, size_t base, size_t cnt, const PassOut& out,
 // the signatures outside G2 (REJ_NOT_IN_SUBGROUP; lanes the decoding already rejected return early)
 static int run_tail(blsv_ctx* c, size_t base, size_t cnt, const PkSel& pk, const PassOut& out, hipStream_t st) {
   const Staging w = staging(c);
-  pairing_check(c, pk, w.H, w.h_inf, w.S, w.s_inf, w.cls, cnt, true, st);
-  return finish_pass(c, base, cnt, out, st);
+  const int rc = pairing_check(c, pk, w.H, w.h_inf, w.S, w.s_inf, w.cls, cnt, true, st);
+  return rc ? rc : finish_pass(c, base, cnt, out, st);
 }
 
 // ---------------------------------------------------------------- randomized batch verification
@@ -146,8 +218,10 @@ static int run_tail_rlc(blsv_ctx* c, size_t base, size_t cnt, const uint32_t (&s
   int rc = rlc_sums(c, base, cnt, seed, st);
   if (rc) return rc;
   HIPCHK(c, hipMemsetAsync(r.gcls.p, 0, ng, st));
-  pairing_check(c, pk, r.gH.as<uint32_t>(), r.g_hinf.as<uint8_t>(), r.gS.as<uint32_t>(), r.g_sinf.as<uint8_t>(),
-                r.gcls.as<uint8_t>(), ng, false, st);
+  // (group sums and failing items are far below one f-pass round: the split rule leaves them whole)
+  rc = pairing_check(c, pk, r.gH.as<uint32_t>(), r.g_hinf.as<uint8_t>(), r.gS.as<uint32_t>(), r.g_sinf.as<uint8_t>(),
+                     r.gcls.as<uint8_t>(), ng, false, st);
+  if (rc) return rc;
   HIPCHK(c, hipGetLastError());
   // sized once for the largest pass and the smallest group: never reallocated under a copy in flight
   HIPCHK(c, r.host.ensure(kMaxChunk / kRlcGroupMin * 5 + 16));
@@ -176,8 +250,9 @@ static int run_tail_rlc(blsv_ctx* c, size_t base, size_t cnt, const uint32_t (&s
                               r.c_hinf.as<uint8_t>(), r.cS.as<uint32_t>(), r.c_sinf.as<uint8_t>(), r.ccls.as<uint8_t>(),
                               st);
     }
-    pairing_check(c, pk, r.cH.as<uint32_t>(), r.c_hinf.as<uint8_t>(), r.cS.as<uint32_t>(), r.c_sinf.as<uint8_t>(),
-                  r.ccls.as<uint8_t>(), m, false, st);
+    rc = pairing_check(c, pk, r.cH.as<uint32_t>(), r.c_hinf.as<uint8_t>(), r.cS.as<uint32_t>(), r.c_sinf.as<uint8_t>(),
+                       r.ccls.as<uint8_t>(), m, false, st);
+    if (rc) return rc;
     StageTimer tm(c, ST_RLC, m, st);
     blsk::launch_rlc_scatter(r.fail.as<uint32_t>(), G, m, r.ccls.as<uint8_t>(), w.cls, cnt, st);
   }

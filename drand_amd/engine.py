@@ -518,6 +518,11 @@ class Engine:
         self._check(self.lib.blsv_test_final_exp(self._h, Fw, n, A, B))
         return list(A)[:n * 144], list(B)[:n * 144]
 
+    def test_tail_split(self, q):
+        """The round a pass is split by (blsv_test_tail_split): q items, 0 = never split, None = the
+        device's own round (one single-lane f-pass wave on every SIMD)."""
+        self._check(self.lib.blsv_test_tail_split(self._h, ctypes.c_size_t(-1).value if q is None else int(q)))
+
     def test_hash_to_g2(self, msgs):
         n = len(msgs)
         lens = (ctypes.c_uint32 * max(n, 1))(*[len(m) for m in msgs])

@@ -30,6 +30,16 @@ int blsv_test_pairing(blsv_ctx* ctx, const uint32_t* p, const uint32_t* q, size_
 int blsv_test_final_exp(blsv_ctx* ctx, const uint32_t* f, size_t n, uint32_t* out_pipeline, uint32_t* out_ref);
 
 /*
+ * The round a pipeline pass is split by: a pass of cnt items with cnt > q and cnt % q != 0 runs the
+ * Miller f pass and the final exponentiation of its last cnt % q items on the side stream, beside the
+ * final exponentiation of the items before them. Production uses one round of the single-lane f pass
+ * (64 lanes x 4 SIMDs x the device's compute units). q items overrides it, 0 turns the split off,
+ * SIZE_MAX restores the device value. blsv_test_final_exp follows the same rule (its two ranges run one
+ * after the other). BLSV_SERIAL_STAGES=1 in the environment keeps every pass whole whatever q is.
+ */
+int blsv_test_tail_split(blsv_ctx* ctx, size_t q);
+
+/*
  * Raw operation hook: one named form of the device field / tower arithmetic (drand_amd/csrc/testops.h
  * lists them: fp_*, fp2_*, the one-reduction linear forms, fp4_*, fp6_*, fp12_*, the Miller f pass's
  * LDS forms and the 3-lane tri_* operations) on n items of operands the caller chooses. An item is
