@@ -111,6 +111,9 @@ SIGNATURES = {
     "blsv_tlock_open": (ctypes.c_int, [vp, u8p, u8p, sz, u8p, u8p, u8p, u8p]),
     "blsv_tlock_open_dev": (ctypes.c_int, [vp, u8p, vp, sz, vp, vp, vp]),
     "blsv_tlock_stats": (ctypes.c_int, [vp, u64p, u64p]),
+    "blsv_tlock_seal": (ctypes.c_int, [vp, u8p, ctypes.c_uint64, u8p, sz, u8p, u8p, u8p]),
+    "blsv_tlock_seal_dev": (ctypes.c_int, [vp, u8p, ctypes.c_uint64, vp, sz, vp, vp, vp, vp]),
+    "blsv_tlock_seal_stats": (ctypes.c_int, [vp, u64p, u64p]),
 }
 
 _lib = None

@@ -336,6 +336,35 @@ def timelock_open(engine, round_: int, sig_v2: bytes, ciphertexts, kdf: Callable
     return out
 
 
+def timelock_seal(engine, round_: int, messages, kdf: Callable[[bytes, int], bytes], scalars=None, pk48=None) -> list:
+    """Locks every message to ``round_`` in ONE engine call (``Engine.tlock_seal``): returns a list of
+    ``(U48, C)`` with ``U = k G1`` and ``C = m XOR kdf(gt, len(m))``, ``gt`` the 576-byte encoding of
+    ``e(pk, H(MessageV2(round_)))^(3k)`` -- what ``timelock_open`` derives from U and the round's
+    SignatureV2. ``pk48=None`` seals under the engine's group key.
+
+    ``scalars=None`` draws one fresh secret scalar in [1, r) per message (``secrets.randbelow``). A
+    caller who passes scalars owns their secrecy and uniqueness; one that is 0 mod r is refused by the
+    engine and raises ``ValueError`` here. ``kdf`` is the caller's, as in ``timelock_open``."""
+    msgs = [bytes(m) for m in messages]
+    if scalars is None:
+        import secrets
+        from .engine import R_ORDER
+        scalars = [secrets.randbelow(R_ORDER - 1) + 1 for _ in msgs]
+    scalars = list(scalars)
+    if len(scalars) != len(msgs):
+        raise ValueError("%d scalars for %d messages" % (len(scalars), len(msgs)))
+    res = engine.tlock_seal(round_, scalars, pk48=pk48)
+    out = []
+    for k, (m, ok, u, gt) in enumerate(zip(msgs, res.ok, res.us, res.gt)):
+        if not ok:
+            raise ValueError("scalar %d is 0 mod r: nothing can be sealed under it" % k)
+        ks = kdf(gt, len(m))
+        if len(ks) != len(m):
+            raise ValueError("kdf returned %d bytes for a %d-byte message" % (len(ks), len(m)))
+        out.append((u, bytes(a ^ b for a, b in zip(m, ks))))
+    return out
+
+
 # --------------------------------------------------------------------------------------------------
 # Threshold aggregation (SURVEY.md §8a row a17): chainStore.runAggregator (chain/beacon/chain.go:91-190)
 # and its partialCache / roundCache (chain/beacon/cache.go:18-182), restated. The cache, the gate and

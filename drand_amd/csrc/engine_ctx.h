@@ -1,5 +1,5 @@
 // Internal to libblsverify.so (never installed, no C ABI): the context object and the helpers the
-// C-ABI entry points (blsverify.cpp, verify.cpp, threshold.cpp, tlock.cpp, testhooks.cpp; their shared
+// C-ABI entry points (blsverify.cpp, verify.cpp, threshold.cpp, tlock.cpp, tseal.cpp, testhooks.cpp; their shared
 // internals are host_internal.h) and the thread-safe service (service.cpp) share.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -68,6 +68,20 @@ static_assert(blsk::G1_WORDS <= blsk::H_WORDS, "timelock: the U table does not f
 static_assert(blsk::F_WORDS <= blsk::HQ_WORDS, "timelock: the captured Fp12 does not fit the HQ staging");
 static_assert(BLSV_GT_LEN == 4 * blsk::F_WORDS, "timelock: the Gt encoding is one F staging row per item");
 static_assert(BLSV_U_LEN <= 4 * blsk::S_WORDS, "timelock: a host call's compressed U bytes do not fit the S staging");
+// Timelock sealing (blsv_tlock_seal*, k_tseal.hip, tseal.cpp) runs in the same staging. A pass of cnt items:
+// a host call's scalars (32 bytes each) in S, cleared before the call returns; the compressed U bytes in H
+// and the ok bytes in h_inf (a device call writes the caller's buffers instead); the class bytes in s_inf;
+// K in HQ (SoA, as the opening captures it) and a host call's encoded bytes in F. The base of a new
+// (key, round), one item through the opening's kernels before the first pass: H(MessageV2(round)) in H /
+// h_inf (HQ between the hash kernels), the decoded key in S / s_inf with its class in cls[0] (cls[1] is
+// the zero class byte launch_tlock_prepare wants beside a hash output), the line table in LN behind the
+// one-item park of the final exponentiation, f in F, B captured in HQ, from where k_tseal_gt_table reads
+// it. The only storage of its own is the two tables (tseal_state).
+static_assert(BLSV_SCALAR_LEN <= 4 * blsk::S_WORDS, "sealing: a host call's scalars do not fit the S staging");
+static_assert(BLSV_U_LEN <= 4 * blsk::H_WORDS, "sealing: the compressed U bytes do not fit the H staging");
+static_assert(blsk::G1_WORDS <= blsk::S_WORDS, "sealing: the decoded key does not fit the S staging");
+static_assert(blsk::FEXP_PARK_WORDS(1) + blsk::kTlockTabWords <= 64 * blsk::MILLER_LINE_WORDS,
+              "sealing: the base's line table does not fit LN behind the park (the smallest workspace is 64 items)");
 
 struct DBuf {
   void* p = nullptr;
@@ -215,6 +229,17 @@ struct tlock_state {
   DBuf d_sig, S, s_inf, s_cls, tab;
 };
 
+// Timelock sealing (blsv_tlock_seal*): the LAST base -- the 48 key bytes and the round it was built
+// for, and T2, the table of its powers. T1 (the generator's multiples) is built once per context. One
+// entry: a call with another key or round replaces it.
+struct tseal_state {
+  bool valid = false, t1_built = false;
+  uint8_t pk[48] = {0};
+  uint64_t round = 0;
+  uint64_t bases = 0, items = 0;  // blsv_tlock_seal_stats
+  DBuf t1, t2;
+};
+
 struct blsv_ctx {
   int device = 0;
   bool prof = false;
@@ -277,6 +302,7 @@ struct blsv_ctx {
   // group with flags and class bytes, the compact staging of the exact fallback, the failing groups
   rlc_state rlc;
   tlock_state tlock;
+  tseal_state tseal;
 };
 
 #define HIPCHK(ctx, expr)                                                             \

@@ -118,6 +118,21 @@ void launch_tlock_f(const uint32_t* tab, const uint32_t* U, const uint8_t* u_inf
                     const uint8_t* sig_inf, size_t cnt, uint32_t* F, hipStream_t st);
 void launch_tlock_encode(const uint32_t* E, const uint8_t* cls, size_t cnt, uint8_t* out, hipStream_t st);
 
+// ---- timelock sealing (k_tseal.hip, tseal.h): U_i = k_i G1, K_i = B^k_i under one shared base B.
+// g1_table: T1 (kTsealT1Words words), the multiples j 16^w G1. gt_table: B = the base's Fp12 (144 words,
+// Montgomery, tower order: a captured final-exponentiation value of stride 1) -> T2 (kTsealT2Words words),
+// the powers B^(j 16^w). u: cnt scalars of 32 bytes big-endian -> us (cnt x 48 bytes), ok and cls (one byte
+// each; a scalar == 0 mod r gets zeros, ok = 0, cls != 0). gt: the same scalars and cls -> E (SoA of stride
+// cnt, what launch_tlock_encode reads; untouched where cls != 0).
+constexpr size_t kTsealT1Words = 64 * 15 * 24;
+constexpr size_t kTsealT2Words = 64 * 15 * 144;
+void launch_tseal_g1_table(uint32_t* T1, hipStream_t st);
+void launch_tseal_gt_table(const uint32_t* B, uint32_t* T2, hipStream_t st);
+void launch_tseal_u(const uint32_t* T1, const uint8_t* scalars, size_t cnt, uint8_t* us, uint8_t* ok, uint8_t* cls,
+                    hipStream_t st);
+void launch_tseal_gt(const uint32_t* T2, const uint8_t* scalars, const uint8_t* cls, size_t cnt, uint32_t* E,
+                     hipStream_t st);
+
 // ---- latency path (k_lat.hip): one workgroup per item, the whole verification; writes cls[i] (REJ_*)
 int lat_trace_read(uint64_t* out, int n, hipStream_t st);  // phase marks of item 0 (wteam.h WV_MARK)
 int lat_trace_clear(hipStream_t st);

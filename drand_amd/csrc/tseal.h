@@ -1,0 +1,147 @@
+// Timelock sealing: n ciphertext heads (U_i, K_i) locked to one round under one key
+// (include/blsverify.h "timelock", blsv_tlock_seal). With B = e(pk, H(MessageV2(round)))^3 computed once
+// (the opening's own kernels, tseal.cpp), item i is U_i = k_i G1 and K_i = B^k_i: two fixed-base
+// operations, so both walk a table of the base's multiples by four-bit windows of k_i,
+//   T1[w][j] = j 16^w G1   (affine, Montgomery; w < 64, j = 1..15;  64 x 15 x 96 B  =  92,160 bytes)
+//   T2[w][j] = B^(j 16^w)  (Fp12, Montgomery, tower order;          64 x 15 x 576 B = 552,960 bytes)
+// one mixed addition / one Fp12 product per non-zero digit, no doubling and no squaring per item.
+// B lies in the cyclotomic subgroup (it left the final exponentiation), so the 64 values B^(16^w) are a
+// chain of 252 Granger-Scott squarings. Table indices depend on the scalar's digits: nothing here is
+// constant-time (as jac_mul_scalar's branches are not for blsv_sign).
+// The shared host/device forms below are what tools/opcount tseal runs and counts; k_tseal.hip holds the
+// device kernels.
+#pragma once
+#include "tlock.h"
+
+namespace bls {
+
+constexpr int TSEAL_WINDOWS = 64;  // four-bit windows of a 256-bit scalar
+constexpr int TSEAL_ENTRIES = 15;  // the non-zero digits
+constexpr int TSEAL_G1_WORDS = 24;   // one T1 entry: x, y
+constexpr int TSEAL_GT_WORDS = 144;  // one T2 entry
+constexpr int TSEAL_T1_WORDS = TSEAL_WINDOWS * TSEAL_ENTRIES * TSEAL_G1_WORDS;
+constexpr int TSEAL_T2_WORDS = TSEAL_WINDOWS * TSEAL_ENTRIES * TSEAL_GT_WORDS;
+constexpr int TSEAL_SCALAR_LEN = 32;
+constexpr uint8_t TSEAL_REFUSED = 1;  // class byte of an item with k == 0 (mod r): encodes as zeros
+
+// entry (w, j), j = 1..15, of either table
+DI int tseal_entry(int w, int j) { return w * TSEAL_ENTRIES + (j - 1); }
+
+// 32 bytes big-endian -> k mod r as eight little-endian words; 2^256 < 3r, so at most two
+// subtractions. Returns false for k == 0 (mod r).
+DI bool tseal_scalar(const uint8_t* be32, uint32_t (&k)[8]) {
+#pragma unroll
+  for (int w = 0; w < 8; w++) {
+    const uint8_t* p = be32 + 4 * (7 - w);
+    k[w] = ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | (uint32_t)p[3];
+  }
+#pragma unroll 1
+  for (int pass = 0; pass < 2; pass++) {
+    uint32_t d[8];
+    uint32_t borrow = 0;
+#pragma unroll
+    for (int w = 0; w < 8; w++) {
+      const uint64_t t = (uint64_t)k[w] - R_ORDER[w] - borrow;
+      d[w] = (uint32_t)t;
+      borrow = (uint32_t)(t >> 63);
+    }
+    if (!borrow) {
+#pragma unroll
+      for (int w = 0; w < 8; w++) k[w] = d[w];
+    }
+  }
+  uint32_t any = 0;
+#pragma unroll
+  for (int w = 0; w < 8; w++) any |= k[w];
+  return any != 0;
+}
+
+DI int tseal_digit(const uint32_t (&k)[8], int w) { return (int)((k[w >> 3] >> ((w & 7) * 4)) & 15u); }
+
+// Row w of T1: 16^w G1 by 4w doublings of the generator, its multiples by repeated addition, each to
+// affine. emit(j, P), j = 1..15.
+template <typename Emit>
+DI void tseal_g1_row(int w, Emit emit) {
+  g1j base = jac_from_aff(g1a{fp_load_const(G1_GEN_X), fp_load_const(G1_GEN_Y)});
+#pragma unroll 1
+  for (int k = 0; k < 4 * w; k++) base = jac_dbl(base);
+  const g1a b = g1_to_aff(base);
+  g1j acc = jac_from_aff(b);
+  emit(1, b);
+#pragma unroll 1
+  for (int j = 2; j <= TSEAL_ENTRIES; j++) {
+    acc = jac_add_aff(acc, b);  // j 16^w < r: never the point at infinity
+    emit(j, g1_to_aff(acc));
+  }
+}
+
+// The chain B^(16^w), w = 0..63: emit(w, v). B must lie in the cyclotomic subgroup.
+template <typename Emit>
+DI void tseal_gt_chain(const fp12& B, Emit emit) {
+  fp12 v = B;
+  emit(0, v);
+#pragma unroll 1
+  for (int w = 1; w < TSEAL_WINDOWS; w++) {
+#pragma unroll 1
+    for (int k = 0; k < 4; k++) v = fp12_cyclotomic_sqr(v);
+    emit(w, v);
+  }
+}
+
+// Row w of T2 beyond its first entry b = B^(16^w): emit(j, b^j), j = 2..15
+template <typename Emit>
+DI void tseal_gt_row(const fp12& b, Emit emit) {
+  fp12 acc = b;
+#pragma unroll 1
+  for (int j = 2; j <= TSEAL_ENTRIES; j++) {
+    acc = fp12_mul(acc, b);
+    emit(j, acc);
+  }
+}
+
+// U = k G1 from T1: one mixed addition per non-zero digit. entry(w, j) returns T1[w][j]. jac_add_aff
+// carries the exceptional cases; with k < r a partial sum is infinity only before the first non-zero
+// digit and never equals +- the addend (the sum of the lower windows is below 16^w <= j 16^w, and their
+// total is below r), so only its first branch is ever taken.
+template <typename Entry>
+DI g1j tseal_u(const uint32_t (&k)[8], Entry entry) {
+  g1j acc = jac_infinity<fp>();
+#pragma unroll 1
+  for (int w = 0; w < TSEAL_WINDOWS; w++) {
+    const int d = tseal_digit(k, w);
+    if (d) acc = jac_add_aff(acc, entry(w, d));
+  }
+  return acc;
+}
+
+// a * b with b fetched by Fp6 halves at their uses (half(0) = c0, half(1) = c1): fp12_mul's Karatsuba,
+// the operand never whole in registers beside the accumulator
+template <typename Half>
+DI fp12 tseal_mul_halves(const fp12& a, Half half) {
+  const fp6 t0 = fp6_mul(a.c0, half(0));
+  const fp6 t1 = fp6_mul(a.c1, half(1));
+  const fp6 c1 = fp6_sub(fp6_sub(fp6_mul(fp6_add_lazy(a.c0, a.c1), fp6_add_lazy(half(0), half(1))), t0), t1);
+  return {fp6_add(t0, fp6_mul_v(t1)), c1};
+}
+
+// K = B^k from T2: the product of one entry per non-zero digit (k != 0). half(w, j, h) returns half h of
+// T2[w][j].
+template <typename Half>
+DI fp12 tseal_gt(const uint32_t (&k)[8], Half half) {
+  fp12 acc = fp12_one();
+  bool first = true;
+#pragma unroll 1
+  for (int w = 0; w < TSEAL_WINDOWS; w++) {
+    const int d = tseal_digit(k, w);
+    if (!d) continue;
+    if (first) {
+      acc = {half(w, d, 0), half(w, d, 1)};
+      first = false;
+    } else {
+      acc = tseal_mul_halves(acc, [&](int h) { return half(w, d, h); });
+    }
+  }
+  return acc;
+}
+
+}  // namespace bls

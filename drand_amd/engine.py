@@ -54,6 +54,32 @@ class TlockResult:
     gt: list
 
 
+# the order r of G1 / G2 / Gt: sealing scalars are taken mod r
+R_ORDER = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
+
+
+@dataclass
+class TsealResult:
+    """Outcome of Engine.tlock_seal: ok[i] (sealed), us[i] = compress(k_i G1), gt[i] = the 576-byte
+    encoding of B^k_i; us[i] and gt[i] are None for a refused scalar (k_i == 0 mod r)."""
+    ok: list
+    us: list
+    gt: list
+
+
+def _scalar32(k):
+    """A sealing scalar as 32 bytes big-endian: an int in [0, 2^256) or 32 bytes already."""
+    if isinstance(k, (bytes, bytearray, memoryview)):
+        k = bytes(k)
+        if len(k) != 32:
+            raise ValueError("scalars are 32 bytes big-endian")
+        return k
+    k = int(k)
+    if not 0 <= k < 1 << 256:
+        raise ValueError("scalars lie in [0, 2^256)")
+    return k.to_bytes(32, "big")
+
+
 def _bits(bitmap, n):
     import numpy as np
     if n == 0:
@@ -411,6 +437,46 @@ class Engine:
         """(signatures prepared, U values processed) since the context was created."""
         a, b = ctypes.c_uint64(), ctypes.c_uint64()
         self._check(self.lib.blsv_tlock_stats(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
+
+    # ------------------------------------------------------------------ timelock sealing
+    # include/blsverify.h "timelock": U_i = k_i G1 and K_i = B^k_i with B = e(pk, H(MessageV2(round)))^3
+    # built once per (key, round); tlock_open(sigma_round, U_i) returns K_i.
+    @staticmethod
+    def _seal_key(pk48):
+        if pk48 is None:
+            return None
+        pk48 = bytes(pk48)
+        if len(pk48) != 48:
+            raise ValueError("the public key is 48 bytes")
+        return _lib.buf(pk48)
+
+    def tlock_seal(self, round_, scalars, pk48=None):
+        """blsv_tlock_seal: TsealResult(ok, us, gt) over `scalars` (ints below 2^256, or 32 bytes
+        big-endian each; taken mod r) locked to `round_` under pk48 (None = the group key). A scalar
+        == 0 (mod r) is refused: ok False, us and gt None. The scalars are the caller's secrets: draw them
+        with `secrets`, fresh per item."""
+        sc = [_scalar32(k) for k in scalars]
+        n = len(sc)
+        us, gt, ok = _lib.out_buf(n * 48), _lib.out_buf(n * 576), _lib.out_buf(n)
+        self._check(self.lib.blsv_tlock_seal(self._h, self._seal_key(pk48), int(round_), _lib.buf(b"".join(sc)), n, us,
+                                             gt, ok))
+        ub, gb = bytes(us), bytes(gt)
+        oks = [bool(x) for x in list(ok)[:n]]
+        return TsealResult(oks, [ub[48 * i:48 * i + 48] if oks[i] else None for i in range(n)],
+                           [gb[576 * i:576 * i + 576] if oks[i] else None for i in range(n)])
+
+    def tlock_seal_dev(self, round_, d_scalars, n, d_us, d_gt, d_ok, pk48=None, stream=None):
+        """blsv_tlock_seal_dev: n device-resident scalars (32 bytes each) -> n x 48 bytes at d_us, n x 576
+        bytes at d_gt (4-byte aligned) and n ok bytes at d_ok; asynchronous on `stream` except for the
+        build of a (key, round) that is not the cached one."""
+        self._check(self.lib.blsv_tlock_seal_dev(self._h, self._seal_key(pk48), int(round_), d_scalars, n, d_us, d_gt,
+                                                 d_ok, stream))
+
+    def tlock_seal_stats(self):
+        """(bases built, scalars processed) since the context was created."""
+        a, b = ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(self.lib.blsv_tlock_seal_stats(self._h, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value
 
     # ------------------------------------------------------------------ stage profiling

@@ -400,6 +400,53 @@ int blsv_tlock_open_dev(blsv_ctx* ctx, const uint8_t* sig96, const uint8_t* d_us
                         uint8_t* d_reject_class, void* stream);
 int blsv_tlock_stats(blsv_ctx* ctx, uint64_t* prepared, uint64_t* items);
 
+/*
+ * Sealing: the producing half, timelock.Encrypt(key.Pairing, G1 base, group key, MessageV2(round), msg)
+ * of the same test, for n messages locked to ONE round. With B = e(pk, H(MessageV2(round)))^3 computed
+ * once, item i is
+ *     out_us48[i]  = compress(k_i * G1)     (the ciphertext's ephemeral point U_i)
+ *     out_gt576[i] = encode(B^k_i)          (K_i, the value the caller's KDF turns into a key stream)
+ * and no item runs a pairing. B is in the convention of blsv_tlock_open -- the same exponent lambda, the
+ * same BLSV_GT_LEN-byte encoding -- so the contract is: for sigma the round's signature under pk,
+ * blsv_tlock_open(sigma, U_i) returns exactly K_i. The masking C = m XOR kdf(K_i) is the caller's.
+ *
+ * Inputs
+ *  - pk48: the compressed G1 key; NULL = the group key (BLSV_ENOGROUP when no group is set). A key that
+ *    does not decode (kilic G1.FromCompressed, subgroup check included) returns BLSV_EINVAL, and so does
+ *    the point at infinity (a seal under it opens for anyone: B = 1); no output is touched in either case.
+ *  - scalars32: n scalars of BLSV_SCALAR_LEN bytes, big-endian, as blsv_sign's sk32; k_i is the value
+ *    mod r. An item with k_i == 0 (mod r) is refused (U would be the point at infinity and K = 1):
+ *    ok[i] = 0 and BLSV_U_LEN + BLSV_GT_LEN zero bytes. Every other item has ok[i] = 1. The caller draws
+ *    the scalars (uniformly in [1, r), fresh per item); the engine draws nothing.
+ *
+ * Secrecy: the scalars are secret until the round arrives. blsv_tlock_seal clears its device staging copy
+ * of them before it returns (the _dev form reads the caller's buffer in place and keeps no copy). There is
+ * NO constant-time claim: both operations walk tables of the base's multiples whose indices are the
+ * scalar's four-bit digits, as blsv_sign's double-and-add branches on the key's bits.
+ *
+ * Base cache: the context keeps the LAST base -- the 48 key bytes, the round, and the table of B's
+ * powers (552,960 bytes on the device; the table of G1's multiples, 92,160 bytes, is built once per
+ * context at the first seal). A call with the same key bytes and round builds nothing; any other key
+ * or round replaces the entry (one entry: A, B, A builds three times). The opening's prepared-signature
+ * cache is separate and survives a seal. blsv_tlock_seal_stats: *bases = bases built, *items = scalars
+ * processed (refused ones included) since the context's creation; either pointer may be NULL.
+ * blsv_tlock_stats is not affected.
+ *
+ * Sizing: the pipeline staging is used as it is; more than a chunk of items runs in chunk-sized passes
+ * with identical outputs. The two tables are the only device memory of its own.
+ *
+ * blsv_tlock_seal_dev: d_scalars32 / d_out_us48 / d_out_gt576 (4-byte aligned) / d_ok are device
+ * pointers, pk48 is host memory. Asynchronous on `stream` under the single-stream rule of
+ * blsv_verify_chained_dev, except that a (key, round) other than the cached one is built first, which
+ * reads the key's decode class back (one synchronisation of `stream`).
+ */
+#define BLSV_SCALAR_LEN 32
+int blsv_tlock_seal(blsv_ctx* ctx, const uint8_t* pk48, uint64_t round, const uint8_t* scalars32, size_t n,
+                    uint8_t* out_us48, uint8_t* out_gt576, uint8_t* ok);
+int blsv_tlock_seal_dev(blsv_ctx* ctx, const uint8_t* pk48, uint64_t round, const uint8_t* d_scalars32, size_t n,
+                        uint8_t* d_out_us48, uint8_t* d_out_gt576, uint8_t* d_ok, void* stream);
+int blsv_tlock_seal_stats(blsv_ctx* ctx, uint64_t* bases, uint64_t* items);
+
 /* ---------------------------------------------------------------- thread-safe service
  *
  * Concurrent single-item callers: the reference verifies each arrival in its own goroutine -- one per

@@ -19,6 +19,7 @@
 #include "../drand_amd/csrc/testops.h"
 #include "../drand_amd/csrc/rlc.h"
 #include "../drand_amd/csrc/tlock.h"
+#include "../drand_amd/csrc/tseal.h"
 
 namespace bls {
 unsigned long long g_fp_mul_count = 0;
@@ -656,6 +657,138 @@ static int cmd_tlock(const char* sighex) {
   return lines_match ? 0 : 1;
 }
 
+static std::string hex_of(const uint8_t* b, size_t n) {
+  std::string h;
+  char t[3];
+  for (size_t k = 0; k < n; k++) {
+    snprintf(t, sizeof t, "%02x", b[k]);
+    h += t;
+  }
+  return h;
+}
+
+// tseal <pk48hex> <round>: the timelock sealing (drand_amd/csrc/tseal.h) as the device runs it -- the base
+// B = e(pk, H(MessageV2(round)))^3 through the opening's own forms (hash, prepared line table, f pass,
+// final exponentiation), the tables T1 (multiples of G1) and T2 (powers of B), then per scalar (stdin, 32
+// bytes big-endian in hex per line) U = k G1 and K = B^k by table walks. "tables_match": every T1 entry
+// equals jac_mul_scalar of the generator and every T2 entry a plain power of B (generic Fp12 squares and
+// products). "u_plain" / "k_plain": the same outputs by a second implementation, jac_mul_scalar and 255
+// cyclotomic squarings with multiplies. A scalar == 0 (mod r) is refused: ok 0 and zero bytes. Prints
+// the Fp products of the base and the tables (once each) and of the last sealed item's four forms.
+static int cmd_tseal(const char* pkhex, unsigned long long round) {
+  const auto pkb = unhex(pkhex);
+  if (pkb.size() != 48) return 2;
+  g1a P;
+  bool pinf;
+  const uint8_t pcls = g1_decompress(pkb.data(), P, pinf);
+  if (pcls != REJ_OK || pinf) {
+    printf("{\"pk_class\": %d, \"pk_inf\": %s}\n", pcls, pinf ? "true" : "false");
+    return 1;
+  }
+  unsigned long long c0 = g_fp_mul_count;
+  fp12 B;
+  {
+    uint32_t msg[8];
+    drand_message_v2(msg, round);
+    const g2a h = g2_to_aff(hash_to_g2(msg));
+    static fp2 lines[MILLER_STEPS][3];
+    tlock_prepare(h, [&](int step, int c, const fp2& v) { lines[step][c] = v; });
+    B = final_exponentiation(tlock_f([&](int step, int c) { return lines[step][c]; }, P.x, P.y));
+  }
+  const unsigned long long n_base = g_fp_mul_count - c0;
+
+  static g1a T1[TSEAL_WINDOWS * TSEAL_ENTRIES];
+  static fp12 T2[TSEAL_WINDOWS * TSEAL_ENTRIES];
+  c0 = g_fp_mul_count;
+  for (int w = 0; w < TSEAL_WINDOWS; w++) tseal_g1_row(w, [&](int j, const g1a& p) { T1[tseal_entry(w, j)] = p; });
+  const unsigned long long n_t1 = g_fp_mul_count - c0;
+  c0 = g_fp_mul_count;
+  tseal_gt_chain(B, [&](int w, const fp12& v) { T2[tseal_entry(w, 1)] = v; });
+  for (int w = 0; w < TSEAL_WINDOWS; w++)
+    tseal_gt_row(T2[tseal_entry(w, 1)], [&](int j, const fp12& v) { T2[tseal_entry(w, j)] = v; });
+  const unsigned long long n_t2 = g_fp_mul_count - c0;
+
+  const g1j G = jac_from_aff(g1a{fp_load_const(G1_GEN_X), fp_load_const(G1_GEN_Y)});
+  bool tables_match = true;
+  {
+    fp12 pw = B;  // B^(16^w) by generic squares
+    for (int w = 0; w < TSEAL_WINDOWS; w++) {
+      if (w)
+        for (int k = 0; k < 4; k++) pw = fp12_sqr(pw);
+      for (int j = 1; j <= TSEAL_ENTRIES; j++) {
+        uint32_t e[8] = {0};
+        e[w >> 3] = (uint32_t)j << ((w & 7) * 4);
+        tables_match &= jac_eq(jac_from_aff(T1[tseal_entry(w, j)]), jac_mul_scalar(G, e));
+        fp12 x = fp12_one();  // pw^j, square and multiply over j's four bits
+        for (int b = 3; b >= 0; b--) {
+          x = fp12_sqr(x);
+          if ((j >> b) & 1) x = fp12_mul(x, pw);
+        }
+        tables_match &= fp12_eq(T2[tseal_entry(w, j)], x);
+      }
+    }
+  }
+
+  std::vector<std::string> us, ks, up, kp;
+  std::vector<int> oks;
+  unsigned long long n_uf = 0, n_gf = 0, n_up = 0, n_gp = 0;
+  static char line_buf[256];
+  while (fgets(line_buf, sizeof line_buf, stdin)) {
+    char* save = nullptr;
+    const char* sh = strtok_r(line_buf, " \n", &save);
+    if (!sh) continue;
+    const auto sb = unhex(sh);
+    if (sb.size() != TSEAL_SCALAR_LEN) return 2;
+    uint32_t k[8];
+    const bool sealed = tseal_scalar(sb.data(), k);
+    oks.push_back(sealed);
+    uint8_t u[48] = {0}, e[TLOCK_GT_LEN] = {0}, u2[48] = {0}, e2[TLOCK_GT_LEN] = {0};
+    if (sealed) {
+      c0 = g_fp_mul_count;
+      g1_compress(u, tseal_u(k, [&](int w, int j) { return T1[tseal_entry(w, j)]; }));
+      n_uf = g_fp_mul_count - c0;
+      c0 = g_fp_mul_count;
+      const fp12 K = tseal_gt(k, [&](int w, int j, int h) {
+        const fp12& t = T2[tseal_entry(w, j)];
+        return h ? t.c1 : t.c0;
+      });
+      n_gf = g_fp_mul_count - c0;
+      tlock_encode(e, K);
+      // the plain way
+      c0 = g_fp_mul_count;
+      g1_compress(u2, jac_mul_scalar(G, k));
+      n_up = g_fp_mul_count - c0;
+      c0 = g_fp_mul_count;
+      fp12 acc = (k[7] >> 31) ? B : fp12_one();
+      for (int b = 254; b >= 0; b--) {
+        acc = fp12_cyclotomic_sqr(acc);
+        if ((k[b >> 5] >> (b & 31)) & 1u) acc = fp12_mul(acc, B);
+      }
+      n_gp = g_fp_mul_count - c0;
+      tlock_encode(e2, acc);
+    }
+    us.push_back(hex_of(u, 48));
+    ks.push_back(hex_of(e, TLOCK_GT_LEN));
+    up.push_back(hex_of(u2, 48));
+    kp.push_back(hex_of(e2, TLOCK_GT_LEN));
+  }
+  auto list = [](const char* name, const std::vector<std::string>& v) {
+    printf("\"%s\": [", name);
+    for (size_t i = 0; i < v.size(); i++) printf("%s\"%s\"", i ? ", " : "", v[i].c_str());
+    printf("], ");
+  };
+  printf("{\"tables_match\": %s, \"ok\": [", tables_match ? "true" : "false");
+  for (size_t i = 0; i < oks.size(); i++) printf("%s%d", i ? ", " : "", oks[i]);
+  printf("], ");
+  list("u", us);
+  list("k", ks);
+  list("u_plain", up);
+  list("k_plain", kp);
+  printf("\"fp_mul\": {\"base\": %llu, \"g1_table\": %llu, \"gt_table\": %llu, \"u_fixed\": %llu, \"gt_fixed\": %llu,"
+         " \"u_plain\": %llu, \"gt_plain\": %llu}}\n", n_base, n_t1, n_t2, n_uf, n_gf, n_up, n_gp);
+  return tables_match ? 0 : 1;
+}
+
 // The batch path's subgroup check of a decoded sigma (not infinity): the call-free line steps of
 // k_miller_lines over |x|'s bits (the lines themselves dropped; they do not depend on the check) and
 // pairing.h miller_t_in_subgroup on the T they leave. close_muls: the Fp products of that closing test.
@@ -702,6 +835,7 @@ static int cmd_subgroup() {
 int main(int argc, char** argv) {
   if (argc == 2 && !strcmp(argv[1], "subgroup")) return cmd_subgroup();
   if (argc == 3 && !strcmp(argv[1], "tlock")) return cmd_tlock(argv[2]);
+  if (argc == 4 && !strcmp(argv[1], "tseal")) return cmd_tseal(argv[2], strtoull(argv[3], nullptr, 10));
   if (argc == 4 && !strcmp(argv[1], "rlc")) return cmd_rlc(argv[2], strtoul(argv[3], nullptr, 10));
   if (argc >= 2 && !strcmp(argv[1], "ops")) return cmd_ops(argc == 3 && !strcmp(argv[2], "list"));
   if (argc == 3 && !strcmp(argv[1], "hash")) return cmd_hash(argv[2]);
@@ -713,8 +847,9 @@ int main(int argc, char** argv) {
   if (argc != 5) {
     fprintf(stderr, "usage: %s pk48hex round prevhex|- sig96hex   (prev '-' = unchained V2)\n       %s hash msghex\n"
             "       %s tlock sig96hex   (one compressed U in hex per line on stdin)\n"
-            "       %s subgroup   (one compressed G2 point in hex per line on stdin)\n",
-            argv[0], argv[0], argv[0], argv[0]);
+            "       %s subgroup   (one compressed G2 point in hex per line on stdin)\n"
+            "       %s tseal pk48hex round   (one 32-byte scalar in hex per line on stdin)\n",
+            argv[0], argv[0], argv[0], argv[0], argv[0]);
     return 2;
   }
   auto pk = unhex(argv[1]);

@@ -13,6 +13,11 @@ run's exact miller + final_exp time, beside the ratio the host-build Fp-product 
 one-item call with a new signature (decode + prepare + one pass) and with the cached one.
 
     python tools/tlock_bench.py --out profiles/tlock_bench.json
+
+--sealed measures the producing side instead (see sealed() below): distinct scalars sealed on the device,
+the result opened, every opened value compared with the sealed one.
+
+    python tools/tlock_bench.py --sealed            # writes profiles/tseal_bench.json on an MI355X
 """
 from __future__ import annotations
 
@@ -59,6 +64,98 @@ def consecutive_points(n):
     return out
 
 
+def sealed(args):
+    """--sealed: n DISTINCT seeded scalars sealed on the device (Engine.tlock_seal_dev) to the golden
+    chain's round 7 under its key, and the resulting U values opened with that round's SignatureV2
+    (Engine.tlock_open_dev). One device comparison checks that every opened value is the sealed K. After
+    warm-up, --pairs interleaved (seal, open) pairs, each timed with a host clock around the call and a
+    device synchronise; medians. Also the fixed cost of a new base (a one-item seal to a new round
+    against one to the cached round)."""
+    import torch
+
+    from drand_amd.engine import Engine
+
+    if not torch.cuda.is_available():
+        raise SystemExit("tlock_bench needs the GPU: nothing here is measured without one")
+    with open(os.path.join(ROOT, "tests", "golden", "golden.json")) as f:
+        ch = json.load(f)["chained"]
+    sig = {b["round"]: bytes.fromhex(b["sig_v2"]) for b in ch["beacons"]}
+    dev = torch.device("cuda", 0)
+    n, round_ = args.items, 7
+    eng = Engine(0)
+    eng.set_public_key(bytes.fromhex(ch["pk"]))
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(2)
+    scalars = torch.randint(0, 256, (n * 32,), dtype=torch.uint8, device=dev, generator=gen)
+    us = torch.empty(n * 48, dtype=torch.uint8, device=dev)
+    ks = torch.empty(n * 576, dtype=torch.uint8, device=dev)
+    ok = torch.empty(n, dtype=torch.uint8, device=dev)
+    opened = torch.empty(n * 576, dtype=torch.uint8, device=dev)
+    cls = torch.empty(n, dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize(dev)
+
+    def seal(r=round_, m=n):
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        eng.tlock_seal_dev(r, scalars.data_ptr(), m, us.data_ptr(), ks.data_ptr(), ok.data_ptr())
+        eng.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    def opening():
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        eng.tlock_open_dev(sig[round_], us.data_ptr(), n, opened.data_ptr(), cls.data_ptr())
+        eng.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    for _ in range(args.warmup):
+        seal()
+        opening()
+    seal_ms, open_ms = [], []
+    for _ in range(args.pairs):
+        seal_ms.append(seal())
+        open_ms.append(opening())
+    all_sealed = int(ok.min().item()) == 1 and int(cls.max().item()) == 0
+    round_trip = bool(torch.equal(opened, ks))
+    distinct_us = int(torch.unique(us.view(n, 48), dim=0).shape[0])
+    eng.profile(True)
+    eng.profile_read()
+    seal()
+    st_seal = {k: round(v[0], 3) for k, v in eng.profile_read().items() if v[1]}
+    eng.profile(False)
+    n1_new, n1_cached = [], []
+    for k in range(args.pairs):
+        n1_new.append(seal(100 + k, 1))
+        n1_cached.append(seal(100 + k, 1))
+    ms, mo = statistics.median(seal_ms), statistics.median(open_ms)
+    counts = json.load(open(os.path.join(ROOT, "profiles", "tseal_opcount.json")))["fp_mul"]
+    opening_counts = json.load(open(os.path.join(ROOT, "profiles", "tlock_opcount.json")))["fp_mul"]
+    res = {"tool": "tools/tlock_bench.py --sealed", "items": n, "distinct_scalars": n, "distinct_us": distinct_us,
+           "pairs": args.pairs, "warmup": args.warmup, "device": torch.cuda.get_device_name(0),
+           "timing": "host clock around the call and a device synchronise; device-resident inputs and outputs",
+           "seal_ms": [round(x, 2) for x in seal_ms], "open_ms": [round(x, 2) for x in open_ms],
+           "seal_ms_median": round(ms, 2), "open_ms_median": round(mo, 2),
+           "seals_per_s": round(n / (ms / 1e3)), "opens_per_s": round(n / (mo / 1e3)),
+           "seal_over_open_measured": round(ms / mo, 3),
+           "seal_over_open_predicted_by_fp_products": round(
+               (counts["u_fixed"] + counts["gt_fixed"]) / (opening_counts["tlock_f"] + opening_counts["final_exp"]), 3),
+           "stage_ms_seal": st_seal,
+           "seal_n1_new_base_ms_median": round(statistics.median(n1_new), 3),
+           "seal_n1_cached_base_ms_median": round(statistics.median(n1_cached), 3),
+           "all_sealed": all_sealed, "open_equals_sealed_k": round_trip,
+           "tlock_seal_stats": eng.tlock_seal_stats(), "tlock_stats": eng.tlock_stats()}
+    # an MI355X reports itself by its architecture; the device name can be a generic one
+    on_mi355x = "gfx950" in getattr(torch.cuda.get_device_properties(0), "gcnArchName", "")
+    out = args.out or (os.path.join(ROOT, "profiles", "tseal_bench.json") if on_mi355x else None)
+    if out:
+        with open(out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+    print(json.dumps(res))
+    eng.close()
+    return 0 if all_sealed and round_trip and distinct_us == n else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--items", type=int, default=1 << 20)
@@ -67,7 +164,11 @@ def main():
     ap.add_argument("--pairs", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--sealed", action="store_true",
+                    help="seal --items distinct scalars on the device and open the result (profiles/tseal_bench.json)")
     args = ap.parse_args()
+    if args.sealed:
+        return sealed(args)
 
     import numpy as np
     import torch
