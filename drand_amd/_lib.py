@@ -114,6 +114,9 @@ SIGNATURES = {
     "blsv_tlock_seal": (ctypes.c_int, [vp, u8p, ctypes.c_uint64, u8p, sz, u8p, u8p, u8p]),
     "blsv_tlock_seal_dev": (ctypes.c_int, [vp, u8p, ctypes.c_uint64, vp, sz, vp, vp, vp, vp]),
     "blsv_tlock_seal_stats": (ctypes.c_int, [vp, u64p, u64p]),
+    "blsv_tlock_seal_rounds": (ctypes.c_int, [vp, u8p, u64p, u8p, sz, u8p, u8p, u8p]),
+    "blsv_tlock_seal_rounds_dev": (ctypes.c_int, [vp, u8p, vp, vp, sz, vp, vp, vp, vp]),
+    "blsv_tlock_seal_rounds_stats": (ctypes.c_int, [vp, u64p, u64p]),
 }
 
 _lib = None

@@ -365,6 +365,33 @@ def timelock_seal(engine, round_: int, messages, kdf: Callable[[bytes, int], byt
     return out
 
 
+def timelock_seal_rounds(engine, items, kdf: Callable[[bytes, int], bytes], scalars=None, pk48=None) -> list:
+    """Locks every ``(round, message)`` of ``items`` to its OWN round in ONE engine call
+    (``Engine.tlock_seal_rounds``): the shape of a sealing service, whose requests pick their unlock
+    times themselves. Returns a list of ``(U48, C)`` in the order of ``items``, each what
+    ``timelock_seal(engine, round, [message], ...)`` gives for its scalar; ``timelock_open`` with the
+    round's SignatureV2 opens it. Scalars, ``kdf`` and ``pk48`` are as in ``timelock_seal``. Many
+    messages for one round are better served by ``timelock_seal`` (no pairing per item)."""
+    items = [(int(r), bytes(m)) for r, m in items]
+    if scalars is None:
+        import secrets
+        from .engine import R_ORDER
+        scalars = [secrets.randbelow(R_ORDER - 1) + 1 for _ in items]
+    scalars = list(scalars)
+    if len(scalars) != len(items):
+        raise ValueError("%d scalars for %d messages" % (len(scalars), len(items)))
+    res = engine.tlock_seal_rounds([r for r, _ in items], scalars, pk48=pk48)
+    out = []
+    for k, ((_, m), ok, u, gt) in enumerate(zip(items, res.ok, res.us, res.gt)):
+        if not ok:
+            raise ValueError("scalar %d is 0 mod r: nothing can be sealed under it" % k)
+        ks = kdf(gt, len(m))
+        if len(ks) != len(m):
+            raise ValueError("kdf returned %d bytes for a %d-byte message" % (len(ks), len(m)))
+        out.append((u, bytes(a ^ b for a, b in zip(m, ks))))
+    return out
+
+
 # --------------------------------------------------------------------------------------------------
 # Threshold aggregation (SURVEY.md §8a row a17): chainStore.runAggregator (chain/beacon/chain.go:91-190)
 # and its partialCache / roundCache (chain/beacon/cache.go:18-182), restated. The cache, the gate and

@@ -1,5 +1,5 @@
 // Internal to libblsverify.so (never installed, no C ABI): the context object and the helpers the
-// C-ABI entry points (blsverify.cpp, verify.cpp, threshold.cpp, tlock.cpp, tseal.cpp, testhooks.cpp; their shared
+// C-ABI entry points (blsverify.cpp, verify.cpp, threshold.cpp, tlock.cpp, tseal.cpp, tsealr.cpp, testhooks.cpp; their shared
 // internals are host_internal.h) and the thread-safe service (service.cpp) share.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -82,6 +82,31 @@ static_assert(BLSV_U_LEN <= 4 * blsk::H_WORDS, "sealing: the compressed U bytes 
 static_assert(blsk::G1_WORDS <= blsk::S_WORDS, "sealing: the decoded key does not fit the S staging");
 static_assert(blsk::FEXP_PARK_WORDS(1) + blsk::kTlockTabWords <= 64 * blsk::MILLER_LINE_WORDS,
               "sealing: the base's line table does not fit LN behind the park (the smallest workspace is 64 items)");
+
+// Timelock sealing to many rounds (blsv_tlock_seal_rounds*, tsealr.cpp, tsealr.h) runs in the same staging,
+// but H holds the hash output H_i until the lines pass has read it, so the one-round seal's plan (U bytes
+// in H, ok bytes in h_inf) does not carry over. A pass of cnt items:
+//   S          no stage of this pass touches it, so it holds everything that is not a stage's own
+//              (hostlogic.h seal_rounds_layout): the table of the points P_i = k_i pk (G1_WORDS each, AoS)
+//              that k_tsealr_point writes and the lines pass reads, and behind it a host call's scalars,
+//              rounds, compressed U bytes and ok bytes (a device call uses the caller's buffers). The points
+//              and the scalars are cleared behind the kernels that read them
+//   s_inf      the class bytes launch_tseal_u writes (0, or TSEAL_REFUSED): read by every later stage
+//   cls        their copy for the final exponentiation, which marks values other than 1 in it
+//   H, h_inf   the hash writes (HQ between its kernels); the lines pass reads, the f pass reads h_inf
+//   LN         the single-pair lines (kMillerLine1Words per item, half the staging) until the f pass has
+//              read them; then the final exponentiation's park, as in a timelock opening
+//   F, FW, HQ  as in a timelock opening: f, the exponentiation's scratch, the captured K_i; a host call's
+//              encoded bytes back in F
+// A new key is decoded into the first entry of S with its flag in s_inf[0] and its class in cls[0], before
+// the first pass; k_tseal_key_table reads it from there. The only storage of its own is the key table.
+static_assert(96 + BLSV_SCALAR_LEN + 8 + BLSV_U_LEN + 1 <= 4 * blsk::S_WORDS,
+              "sealing to many rounds: the P table, scalars, rounds, U and ok bytes do not fit the S staging");
+static_assert(96 == 4 * blsk::G1_WORDS && (96 + BLSV_SCALAR_LEN) % 8 == 0,
+              "sealing to many rounds: seal_rounds_layout's P entry, and the alignment of the rounds behind the scalars");
+static_assert(blsk::kMillerLine1Words <= blsk::MILLER_LINE_WORDS &&
+                  blsk::FEXP_PARK_WORDS(kMaxChunk) <= blsk::MILLER_LINE_WORDS * kMaxChunk,
+              "sealing to many rounds: the single-pair lines, then the park, do not fit LN");
 
 struct DBuf {
   void* p = nullptr;
@@ -240,6 +265,15 @@ struct tseal_state {
   DBuf t1, t2;
 };
 
+// Timelock sealing to many rounds (blsv_tlock_seal_rounds*): the LAST key -- its 48 bytes and TK, the
+// table of its multiples (T1's layout). One entry: a call with another key replaces it.
+struct tsealr_state {
+  bool valid = false;
+  uint8_t pk[48] = {0};
+  uint64_t keys = 0, items = 0;  // blsv_tlock_seal_rounds_stats
+  DBuf tk;
+};
+
 struct blsv_ctx {
   int device = 0;
   bool prof = false;
@@ -303,6 +337,7 @@ struct blsv_ctx {
   rlc_state rlc;
   tlock_state tlock;
   tseal_state tseal;
+  tsealr_state tsealr;
 };
 
 #define HIPCHK(ctx, expr)                                                             \

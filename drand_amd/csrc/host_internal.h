@@ -1,5 +1,5 @@
 // Internal to the HIP-side host units of libblsverify.so (blsverify.cpp, verify.cpp, threshold.cpp,
-// tlock.cpp, testhooks.cpp): the pinned small copies, stage timing, the typed view of the pipeline
+// tlock.cpp, tseal.cpp, tsealr.cpp, testhooks.cpp): the pinned small copies, stage timing, the typed view of the pipeline
 // staging with its launch wrappers, and the one pass loop every verification entry point runs.
 #pragma once
 #include <functional>
@@ -156,5 +156,8 @@ int stage_chain(blsv_ctx* c, uint64_t first_round, const uint8_t* prevs, size_t 
 int decode_g1(blsv_ctx* c, const uint8_t* pk48, size_t cnt, DBuf& tab, DBuf& inf, std::vector<uint8_t>& cls);
 // n messages packed back to back (msg_lens[i] bytes each) into in_msgs / in_off / in_len
 int upload_messages(blsv_ctx* c, const uint8_t* msgs, const uint32_t* msg_lens, size_t n);
+
+// ---- tseal.cpp: the key a sealing call runs under -- pk48, or the group key (BLSV_ENOGROUP without one)
+int seal_key(blsv_ctx* c, const uint8_t* pk48, const uint8_t** key);
 
 #pragma GCC visibility pop

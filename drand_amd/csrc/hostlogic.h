@@ -276,5 +276,27 @@ inline SvcLayout svc_layout(size_t n, size_t mbytes) {
   return l;
 }
 
+// blsv_tlock_seal_rounds*: whether the byte counts of n items (the largest array is the n x 576 bytes of
+// encoded values) fit size_t
+inline bool seal_rounds_fits(size_t n) { return n <= SIZE_MAX / BLSV_GT_LEN; }
+// ... and what a pass of cnt items keeps in the S staging (192 bytes per item; every stage of the pass
+// leaves S alone): the table of the points P_i = k_i pk (96 bytes each) first, then a host call's scalars
+// (32 each), rounds (8 each; the offset is a multiple of 8), compressed U bytes (48 each) and ok bytes.
+// [0, secret) is what the entry points clear behind the kernels: the points and the scalars.
+struct SealRoundsLayout {
+  size_t o_p, o_scalars, o_rounds, o_us, o_ok, total, secret;
+};
+inline SealRoundsLayout seal_rounds_layout(size_t cnt) {
+  SealRoundsLayout l;
+  l.o_p = 0;
+  l.o_scalars = l.o_p + cnt * 96;
+  l.o_rounds = l.o_scalars + cnt * BLSV_SCALAR_LEN;
+  l.o_us = l.o_rounds + cnt * 8;
+  l.o_ok = l.o_us + cnt * BLSV_U_LEN;
+  l.total = l.o_ok + cnt;
+  l.secret = l.o_rounds;
+  return l;
+}
+
 }  // namespace blsv_detail
 #pragma GCC visibility pop

@@ -11,53 +11,17 @@
 #include <type_traits>
 
 #include "kcommon.h"
+#include "kmiller.h"
 #include "testops.h"
 
 namespace blsk {
 
 // line slot of (step, pair): 6 Fp slots (a0, a1, a4 as Fp2)
 DI int line_slot(int step, int k) { return (step * 2 + k) * 6; }
-// cache policy of the line staging's stores and loads (soa.h AUX; 0 = default)
-// Cache policy of the line staging: written once by k_miller_lines, read once by k_miller_f, 13.8 KB
-// per beacon -- nothing to keep in L2/MALL. Non-temporal (gfx950 aux 2) on both sides: Miller
-// 196.2 -> 192.7 ms per 1M on one box, interleaved twice (profiles/r06s_ln_nt_ab.json); the loads
-// carry the gain, the stores alone change nothing.
-#ifndef BLS_LN_AUX
-#define BLS_LN_AUX 2
-#endif
-#ifndef BLS_LN_AUX_ST
-#define BLS_LN_AUX_ST BLS_LN_AUX
-#endif
-#ifndef BLS_LN_AUX_LD
-#define BLS_LN_AUX_LD BLS_LN_AUX
-#endif
-
 // Item g = base + i of the chunk (H/S/F/cls stride cnt); its lines at LN index i (stride sub).
 // The two pairs run in separate workgroups (k = blockIdx.x & 1: the pair of the whole wave), so a
 // beacon's two line chains run side by side: half the latency of one lane walking both, twice the
 // waves (a finer tail), and every store still one 256-byte access per wave.
-static __shared__ uint32_t g_ml_T[72 * BLS_LANES];
-// T = (X, Y, Z) in LDS, word w of coordinate c at [(24 c + w) * 64 + lane]: conflict-free dword access
-struct g2proj_lds {
-  uint32_t* base;
-  DI fp2 get(int c) const {
-    fp2 v;
-#pragma unroll
-    for (int w = 0; w < 12; w++) {
-      v.c0.l[w] = base[(24 * c + w) * BLS_LANES];
-      v.c1.l[w] = base[(24 * c + 12 + w) * BLS_LANES];
-    }
-    return v;
-  }
-  DI void set(int c, const fp2& v) const {
-#pragma unroll
-    for (int w = 0; w < 12; w++) {
-      base[(24 * c + w) * BLS_LANES] = v.c0.l[w];
-      base[(24 * c + 12 + w) * BLS_LANES] = v.c1.l[w];
-    }
-  }
-};
-
 // CHECK: the k == 1 workgroups (the pair (-g1, sigma)) also close sigma's psi subgroup check on their
 // own T, which is [|x|]sigma when the loop ends (pairing.h miller_t_in_subgroup), and write
 // cls[g] = REJ_NOT_IN_SUBGROUP on a failure: the per-item batch path, whose head then only decodes.
@@ -162,10 +126,6 @@ DI fp2 mf_get(int c) {
   }
   return v;
 }
-// q p of the one-reduction linear forms (tower.h fp2_lin_reduce, T < 16p) from an LDS table of k p,
-// k < 16 (768 bytes per workgroup, tower.h kp_lds_init / KpLdsK)
-using KpLds16 = KpLdsK<16>;
-
 // fp6_mul(a, b) (tower.h, Karatsuba) with b's components read through lb
 template <typename LB>
 DI fp6 fp6_mul_lb(const fp6& a, LB lb) {

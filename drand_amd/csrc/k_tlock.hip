@@ -77,16 +77,6 @@ DI fp2 tl_get(int step, int c) {
   return v;
 }
 
-// tower.h fp12_mul_by_014 with the line read through l(c) at each use. (Forming c first, so that a, b
-// and c are never all live with f, costs scratch instead of saving it: 320 bytes per lane against 224.)
-template <typename L>
-DI fp12 fp12_mul_by_014_l(const fp12& f, L l) {
-  const fp6 a = fp6_mul_by_01(f.c0, l(0), l(1));
-  const fp6 b = fp6_mul_by_1(f.c1, l(2));
-  const fp6 c = fp6_mul_by_01(fp6_add_lazy(f.c0, f.c1), l(0), fp2_add_lazy(l(1), l(2)));
-  return {fp6_add(a, fp6_mul_v(b)), fp6_sub(fp6_sub(c, a), b)};
-}
-
 using KpLds16T = KpLdsK<16>;
 
 // U: the AoS table launch_decompress_g1 wrote (G1_WORDS per item) with u_inf / cls; F: SoA of stride cnt.

@@ -133,6 +133,22 @@ void launch_tseal_u(const uint32_t* T1, const uint8_t* scalars, size_t cnt, uint
 void launch_tseal_gt(const uint32_t* T2, const uint8_t* scalars, const uint8_t* cls, size_t cnt, uint32_t* E,
                      hipStream_t st);
 
+// ---- timelock sealing to many rounds (k_tsealr.hip, tsealr.h): K_i = e(k_i pk, H(MessageV2(round_i)))^3, one
+// single-pair pairing per item. key_table: key = a one-entry table of launch_decompress_g1 (a point of
+// order r, not infinity) -> TK (kTsealT1Words words), the multiples j 16^w pk. point: the scalars and cls
+// of launch_tseal_u -> P, an AoS table of G1_WORDS per item with P_i = k_i pk (untouched where cls != 0).
+// miller_lines1 / miller_f1: the two Miller passes of the pairs (P_i, H_i) alone over a
+// whole pass of cnt items; LN holds kMillerLine1Words per item, half of MILLER_LINE_WORDS; F as
+// launch_miller leaves it (1 where h_inf, untouched where cls != 0).
+constexpr size_t kMillerLine1Words = 68 * 6 * 12;
+void launch_tseal_key_table(const uint32_t* key, uint32_t* TK, hipStream_t st);
+void launch_tsealr_point(const uint32_t* TK, const uint8_t* scalars, const uint8_t* cls, size_t cnt, uint32_t* P,
+                         hipStream_t st);
+void launch_miller_lines1(const uint32_t* P, const uint32_t* H, const uint8_t* h_inf, const uint8_t* cls, size_t cnt,
+                          uint32_t* LN, hipStream_t st);
+void launch_miller_f1(const uint32_t* LN, const uint8_t* h_inf, const uint8_t* cls, size_t cnt, uint32_t* F,
+                      hipStream_t st);
+
 // ---- latency path (k_lat.hip): one workgroup per item, the whole verification; writes cls[i] (REJ_*)
 int lat_trace_read(uint64_t* out, int n, hipStream_t st);  // phase marks of item 0 (wteam.h WV_MARK)
 int lat_trace_clear(hipStream_t st);

@@ -44,6 +44,17 @@ DI line tlock_line(Coef coef, int step, const fp& xu, const fp& yu) {
   return {coef(step, 0), fp2_mul_fp(coef(step, 1), xu), fp2_mul_fp(coef(step, 2), yu)};
 }
 
+// tower.h fp12_mul_by_014 with the line read through l(c) at each use (k_tlock_f: from LDS; the
+// single-pair f pass of tsealr.h: from the line staging). (Forming c first, so that a, b and c are never
+// all live with f, costs scratch instead of saving it: 320 bytes per lane against 224 in k_tlock_f.)
+template <typename L>
+DI fp12 fp12_mul_by_014_l(const fp12& f, L l) {
+  const fp6 a = fp6_mul_by_01(f.c0, l(0), l(1));
+  const fp6 b = fp6_mul_by_1(f.c1, l(2));
+  const fp6 c = fp6_mul_by_01(fp6_add_lazy(f.c0, f.c1), l(0), fp2_add_lazy(l(1), l(2)));
+  return {fp6_add(a, fp6_mul_v(b)), fp6_sub(fp6_sub(c, a), b)};
+}
+
 // register form of the f pass (host op counter; k_tlock_f is the device form)
 template <typename Coef>
 DI fp12 tlock_f(Coef coef, const fp& xu, const fp& yu) {

@@ -106,8 +106,8 @@ static int seal_passes(blsv_ctx* c, bool host, const uint8_t* scalars, size_t n,
   return BLSV_OK;
 }
 
-// the key a call seals under: pk48, or the group key
-static int seal_key(blsv_ctx* c, const uint8_t* pk48, const uint8_t** key) {
+// the key a call seals under: pk48, or the group key (shared with tsealr.cpp)
+int seal_key(blsv_ctx* c, const uint8_t* pk48, const uint8_t** key) {
   if (pk48) {
     *key = pk48;
     return BLSV_OK;

@@ -58,11 +58,11 @@ DI bool tseal_scalar(const uint8_t* be32, uint32_t (&k)[8]) {
 
 DI int tseal_digit(const uint32_t (&k)[8], int w) { return (int)((k[w >> 3] >> ((w & 7) * 4)) & 15u); }
 
-// Row w of T1: 16^w G1 by 4w doublings of the generator, its multiples by repeated addition, each to
-// affine. emit(j, P), j = 1..15.
+// Row w of the table of a base point A of order r (T1's layout): 16^w A by 4w doublings, its multiples by
+// repeated addition, each to affine. emit(j, P), j = 1..15.
 template <typename Emit>
-DI void tseal_g1_row(int w, Emit emit) {
-  g1j base = jac_from_aff(g1a{fp_load_const(G1_GEN_X), fp_load_const(G1_GEN_Y)});
+DI void tseal_g1_row_of(const g1a& A, int w, Emit emit) {
+  g1j base = jac_from_aff(A);
 #pragma unroll 1
   for (int k = 0; k < 4 * w; k++) base = jac_dbl(base);
   const g1a b = g1_to_aff(base);
@@ -73,6 +73,11 @@ DI void tseal_g1_row(int w, Emit emit) {
     acc = jac_add_aff(acc, b);  // j 16^w < r: never the point at infinity
     emit(j, g1_to_aff(acc));
   }
+}
+// Row w of T1: the generator's
+template <typename Emit>
+DI void tseal_g1_row(int w, Emit emit) {
+  tseal_g1_row_of(g1a{fp_load_const(G1_GEN_X), fp_load_const(G1_GEN_Y)}, w, emit);
 }
 
 // The chain B^(16^w), w = 0..63: emit(w, v). B must lie in the cyclotomic subgroup.

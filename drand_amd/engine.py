@@ -479,6 +479,41 @@ class Engine:
         self._check(self.lib.blsv_tlock_seal_stats(self._h, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value
 
+    # ------------------------------------------------------------------ timelock sealing to many rounds
+    # include/blsverify.h "timelock": item i locked to rounds[i]; its outputs are those of
+    # tlock_seal(rounds[i], [scalars[i]]). One single-pair pairing per item, no base shared or cached.
+    def tlock_seal_rounds(self, rounds, scalars, pk48=None):
+        """blsv_tlock_seal_rounds: TsealResult(ok, us, gt), item i sealing scalars[i] (as tlock_seal takes
+        them) to rounds[i] (any uint64) under pk48 (None = the group key). A scalar == 0 (mod r) is
+        refused: ok False, us and gt None."""
+        rounds = [int(r) for r in rounds]
+        sc = [_scalar32(k) for k in scalars]
+        n = len(sc)
+        if len(rounds) != n:
+            raise ValueError("%d rounds for %d scalars" % (len(rounds), n))
+        if any(not 0 <= r < 1 << 64 for r in rounds):
+            raise ValueError("a round is a uint64")
+        us, gt, ok = _lib.out_buf(n * 48), _lib.out_buf(n * 576), _lib.out_buf(n)
+        self._check(self.lib.blsv_tlock_seal_rounds(self._h, self._seal_key(pk48), (ctypes.c_uint64 * n)(*rounds),
+                                                    _lib.buf(b"".join(sc)), n, us, gt, ok))
+        ub, gb = bytes(us), bytes(gt)
+        oks = [bool(x) for x in list(ok)[:n]]
+        return TsealResult(oks, [ub[48 * i:48 * i + 48] if oks[i] else None for i in range(n)],
+                           [gb[576 * i:576 * i + 576] if oks[i] else None for i in range(n)])
+
+    def tlock_seal_rounds_dev(self, d_rounds, d_scalars, n, d_us, d_gt, d_ok, pk48=None, stream=None):
+        """blsv_tlock_seal_rounds_dev: n device-resident rounds (uint64 each, 8-byte aligned) and scalars
+        (32 bytes each) -> n x 48 bytes at d_us, n x 576 bytes at d_gt (4-byte aligned) and n ok bytes at
+        d_ok; asynchronous on `stream` except for the decode of a key that is not the cached one."""
+        self._check(self.lib.blsv_tlock_seal_rounds_dev(self._h, self._seal_key(pk48), d_rounds, d_scalars, n, d_us,
+                                                        d_gt, d_ok, stream))
+
+    def tlock_seal_rounds_stats(self):
+        """(key tables built, scalars processed) since the context was created."""
+        a, b = ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(self.lib.blsv_tlock_seal_rounds_stats(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
+
     # ------------------------------------------------------------------ stage profiling
     STAGES = ("hash", "decompress", "miller", "final_exp", "finish", "lat", "rlc", "tlock")
 

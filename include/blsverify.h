@@ -447,6 +447,51 @@ int blsv_tlock_seal_dev(blsv_ctx* ctx, const uint8_t* pk48, uint64_t round, cons
                         uint8_t* d_out_us48, uint8_t* d_out_gt576, uint8_t* d_ok, void* stream);
 int blsv_tlock_seal_stats(blsv_ctx* ctx, uint64_t* bases, uint64_t* items);
 
+/*
+ * Sealing to many rounds: n messages, item i locked to its OWN round rounds[i] under one key -- the shape
+ * of a sealing service or relay, whose requests (round_i, message_i) pick their unlock times themselves.
+ * Item i's outputs are byte for byte those of blsv_tlock_seal(ctx, pk48, rounds[i], scalars32 + 32 i, 1, ...):
+ *     out_us48[i]  = compress(k_i * G1)
+ *     out_gt576[i] = encode(e(pk, H(MessageV2(rounds[i])))^(3 k_i))
+ * so blsv_tlock_open(sigma_{rounds[i]}, U_i) returns exactly K_i. No base is shared between items: each
+ * runs one single-pair pairing e(k_i pk, H_i) of its own (k_i pk by a walk over a table of pk's
+ * multiples), and the items of a pass run side by side. Any uint64 is a valid round.
+ * Measured on one MI355X (profiles/tseal_rounds_bench.json): 64 items with 64 distinct
+ * rounds take 17.7 ms in one call against 2,195 ms as 64 one-item blsv_tlock_seal calls; 1 Mi items with
+ * 1 Mi distinct rounds seal at 2.80 M/s, beside 12.7 M/s for the same scalars to one round. A caller with
+ * many items per round is better served by blsv_tlock_seal, which runs no pairing per item: a loop of it
+ * over the rounds wins from somewhere between 65,536 and 262,144 items per distinct round.
+ *
+ * pk48, scalars32, ok and the refusal of k_i == 0 (mod r) -- ok[i] = 0 and BLSV_U_LEN + BLSV_GT_LEN zero
+ * bytes, neighbours unaffected -- are blsv_tlock_seal's: NULL = the group key (BLSV_ENOGROUP without one);
+ * a key that does not decode, or the point at infinity, returns BLSV_EINVAL and no output is touched.
+ *
+ * Secrecy: the host entry clears its device staging copy of the scalars before it returns, and both
+ * entries clear the staged points k_i pk (each is as good as K_i to whoever holds it), behind the kernels
+ * that read them and also when a pass fails. There is NO constant-time claim, as above.
+ *
+ * Key cache: the context keeps the table of the LAST key's multiples (92,160 bytes on the device), keyed
+ * by the 48 key bytes. A call under the same key builds nothing; another key replaces the entry (A, B, A
+ * builds three times). blsv_tlock_seal_rounds_stats: *keys = key tables built, *items = scalars
+ * processed (refused ones included); either pointer may be NULL. blsv_tlock_seal_stats and
+ * blsv_tlock_stats do not move, and the one-round base cache and the opening's prepared-signature cache
+ * survive a call.
+ *
+ * Sizing: the pipeline staging is used as it is; more than a chunk of items runs in chunk-sized passes
+ * with identical outputs. The key table is the only device memory of its own.
+ *
+ * blsv_tlock_seal_rounds_dev: d_rounds (8-byte aligned) / d_scalars32 / d_out_us48 / d_out_gt576 (4-byte
+ * aligned) / d_ok are device pointers, pk48 is host memory. Asynchronous on `stream` under the
+ * single-stream rule of blsv_verify_chained_dev, except that a key other than the cached one has its
+ * decode class read back (one synchronisation of `stream`).
+ */
+int blsv_tlock_seal_rounds(blsv_ctx* ctx, const uint8_t* pk48, const uint64_t* rounds, const uint8_t* scalars32,
+                           size_t n, uint8_t* out_us48, uint8_t* out_gt576, uint8_t* ok);
+int blsv_tlock_seal_rounds_dev(blsv_ctx* ctx, const uint8_t* pk48, const uint64_t* d_rounds,
+                               const uint8_t* d_scalars32, size_t n, uint8_t* d_out_us48, uint8_t* d_out_gt576,
+                               uint8_t* d_ok, void* stream);
+int blsv_tlock_seal_rounds_stats(blsv_ctx* ctx, uint64_t* keys, uint64_t* items);
+
 /* ---------------------------------------------------------------- thread-safe service
  *
  * Concurrent single-item callers: the reference verifies each arrival in its own goroutine -- one per

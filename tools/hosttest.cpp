@@ -350,7 +350,27 @@ int test_hostlogic() {
              std::to_string(l.o_sig) + ", " + std::to_string(l.o_msg) + ", " + std::to_string(l.total) + "]";
     }
   }
-  out += "]}}";
+  out += "], \"seal_rounds\": {\"fits\": [";
+  {
+    // blsv_tlock_seal_rounds*: the guard on n at both sides of its limit, and the S-staging layout of a pass
+    const size_t lim = SIZE_MAX / BLSV_GT_LEN;
+    const size_t ns[6] = {0, 1, size_t(1) << 20, lim, lim + 1, SIZE_MAX};
+    for (int k = 0; k < 6; k++) {
+      const bool fits = seal_rounds_fits(ns[k]);
+      if (fits) CHECK(ns[k] * BLSV_GT_LEN / BLSV_GT_LEN == ns[k]);  // no byte count of the call wraps
+      out += std::string(k ? ", " : "") + (fits ? "true" : "false");
+    }
+    out += "], \"layout\": [";
+    const size_t cnts[4] = {1, 64, 16384, size_t(1) << 20};
+    for (int k = 0; k < 4; k++) {
+      const SealRoundsLayout l = seal_rounds_layout(cnts[k]);
+      CHECK(l.o_rounds % 8 == 0 && l.o_p % 4 == 0 && l.total <= 192 * cnts[k] && l.secret == l.o_rounds);
+      out += std::string(k ? ", " : "") + "[" + std::to_string(l.o_p) + ", " + std::to_string(l.o_scalars) + ", " +
+             std::to_string(l.o_rounds) + ", " + std::to_string(l.o_us) + ", " + std::to_string(l.o_ok) + ", " +
+             std::to_string(l.total) + ", " + std::to_string(l.secret) + "]";
+    }
+  }
+  out += "]}}}";
   puts(out.c_str());
   return 0;
 }

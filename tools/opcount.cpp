@@ -20,6 +20,7 @@
 #include "../drand_amd/csrc/rlc.h"
 #include "../drand_amd/csrc/tlock.h"
 #include "../drand_amd/csrc/tseal.h"
+#include "../drand_amd/csrc/tsealr.h"
 
 namespace bls {
 unsigned long long g_fp_mul_count = 0;
@@ -789,6 +790,126 @@ static int cmd_tseal(const char* pkhex, unsigned long long round) {
   return tables_match ? 0 : 1;
 }
 
+// tsealr <pk48hex>: the timelock sealing to many rounds (drand_amd/csrc/tsealr.h) as the device runs it.
+// Per line of stdin, "round scalarhex" (the round in decimal, 32 bytes big-endian in hex): U = k G1 from
+// T1, P = k pk by the walk over the key table TK, H = H(MessageV2(round)), the single-pair lines of
+// (P, H), the single-pair f pass over them, the final exponentiation and the Gt encoding. "table_match":
+// every TK entry equals jac_mul_scalar of pk. "u_plain" / "k_plain": the same outputs by a second
+// implementation, jac_mul_scalar for both points and miller_loop_multi<1> with the register final
+// exponentiation. A scalar == 0 (mod r) is refused: ok 0 and zero bytes.
+// Prints the Fp products of the key table (once) and of the last sealed item's stages, and beside them
+// what the two-pair passes cost for the same item: "lines2" walks a second chain next to (P, H) -- the
+// pair (-G1, H) as a stand-in, what a pass with a live second pair pays -- and "f2" is
+// miller_f_from_lines with the second pair inactive (its lines 1), which must give the single-pair f
+// ("two_pair_match").
+static int cmd_tsealr(const char* pkhex) {
+  const auto pkb = unhex(pkhex);
+  if (pkb.size() != 48) return 2;
+  g1a PK;
+  bool pinf;
+  const uint8_t pcls = g1_decompress(pkb.data(), PK, pinf);
+  if (pcls != REJ_OK || pinf) {
+    printf("{\"pk_class\": %d, \"pk_inf\": %s}\n", pcls, pinf ? "true" : "false");
+    return 1;
+  }
+  static g1a T1[TSEAL_WINDOWS * TSEAL_ENTRIES], TK[TSEAL_WINDOWS * TSEAL_ENTRIES];
+  for (int w = 0; w < TSEAL_WINDOWS; w++) tseal_g1_row(w, [&](int j, const g1a& p) { T1[tseal_entry(w, j)] = p; });
+  unsigned long long c0 = g_fp_mul_count;
+  for (int w = 0; w < TSEAL_WINDOWS; w++)
+    tseal_g1_row_of(PK, w, [&](int j, const g1a& p) { TK[tseal_entry(w, j)] = p; });
+  const unsigned long long n_tk = g_fp_mul_count - c0;
+  const g1j G = jac_from_aff(g1a{fp_load_const(G1_GEN_X), fp_load_const(G1_GEN_Y)}), PKJ = jac_from_aff(PK);
+  bool table_match = true;
+  for (int w = 0; w < TSEAL_WINDOWS; w++)
+    for (int j = 1; j <= TSEAL_ENTRIES; j++) {
+      uint32_t e[8] = {0};
+      e[w >> 3] = (uint32_t)j << ((w & 7) * 4);
+      table_match &= jac_eq(jac_from_aff(TK[tseal_entry(w, j)]), jac_mul_scalar(PKJ, e));
+    }
+
+  std::vector<std::string> us, ks, up, kp;
+  std::vector<int> oks;
+  bool two_pair_match = true;
+  unsigned long long n_u = 0, n_p = 0, n_l1 = 0, n_f1 = 0, n_fexp = 0, n_l2 = 0, n_f2 = 0;
+  static char line_buf[256];
+  while (fgets(line_buf, sizeof line_buf, stdin)) {
+    char* save = nullptr;
+    const char* rh = strtok_r(line_buf, " \n", &save);
+    const char* sh = rh ? strtok_r(nullptr, " \n", &save) : nullptr;
+    if (!rh) continue;
+    if (!sh) return 2;
+    const unsigned long long round = strtoull(rh, nullptr, 10);
+    const auto sb = unhex(sh);
+    if (sb.size() != TSEAL_SCALAR_LEN) return 2;
+    uint32_t k[8];
+    const bool sealed = tseal_scalar(sb.data(), k);
+    oks.push_back(sealed);
+    uint8_t u[48] = {0}, e[TLOCK_GT_LEN] = {0}, u2[48] = {0}, e2[TLOCK_GT_LEN] = {0};
+    if (sealed) {
+      c0 = g_fp_mul_count;
+      g1_compress(u, tseal_u(k, [&](int w, int j) { return T1[tseal_entry(w, j)]; }));
+      n_u = g_fp_mul_count - c0;
+      c0 = g_fp_mul_count;
+      const g1a P = tsealr_point(k, [&](int w, int j) { return TK[tseal_entry(w, j)]; });
+      n_p = g_fp_mul_count - c0;
+      uint32_t msg[8];
+      drand_message_v2(msg, round);
+      const g2a H = g2_to_aff(hash_to_g2(msg));
+      auto load_h = [&]() { return H; };
+      static fp2 L[MILLER_STEPS][3];
+      g2proj T;
+      c0 = g_fp_mul_count;
+      tsealr_lines(g2proj_reg{T}, load_h, [&](int step, int c, const fp2& v) { L[step][c] = v; },
+                   [&]() { return P.x; }, [&]() { return P.y; });
+      n_l1 = g_fp_mul_count - c0;
+      c0 = g_fp_mul_count;
+      const fp12 f = tsealr_f([&](int step, int c) { return L[step][c]; }, [](const fp12& a) { return fp12_sqr(a); });
+      n_f1 = g_fp_mul_count - c0;
+      c0 = g_fp_mul_count;
+      const fp12 K = final_exponentiation(f);
+      n_fexp = g_fp_mul_count - c0;
+      tlock_encode(e, K);
+      // the two-pair passes for the same item
+      c0 = g_fp_mul_count;
+      g2proj T2;
+      tsealr_lines(g2proj_reg{T2}, load_h, [](int, int, const fp2&) {}, []() { return fp_load_const(G1_GEN_X); },
+                   []() { return fp_load_const(G1_GEN_NEG_Y); });
+      n_l2 = n_l1 + (g_fp_mul_count - c0);
+      c0 = g_fp_mul_count;
+      const fp12 f2 = miller_f_from_lines(
+          [&](int step, int pair) { return pair == 0 ? line{L[step][0], L[step][1], L[step][2]} : line_one(); });
+      n_f2 = g_fp_mul_count - c0;
+      two_pair_match &= fp12_eq(f, f2);
+      // the plain way
+      g1_compress(u2, jac_mul_scalar(G, k));
+      const g1a Ps[1] = {g1_to_aff(jac_mul_scalar(PKJ, k))};
+      const g2a Qs[1] = {H};
+      const bool act[1] = {true};
+      tlock_encode(e2, final_exponentiation(miller_loop_multi<1>(Ps, Qs, act)));
+    }
+    us.push_back(hex_of(u, 48));
+    ks.push_back(hex_of(e, TLOCK_GT_LEN));
+    up.push_back(hex_of(u2, 48));
+    kp.push_back(hex_of(e2, TLOCK_GT_LEN));
+  }
+  auto list = [](const char* name, const std::vector<std::string>& v) {
+    printf("\"%s\": [", name);
+    for (size_t i = 0; i < v.size(); i++) printf("%s\"%s\"", i ? ", " : "", v[i].c_str());
+    printf("], ");
+  };
+  printf("{\"table_match\": %s, \"two_pair_match\": %s, \"ok\": [", table_match ? "true" : "false",
+         two_pair_match ? "true" : "false");
+  for (size_t i = 0; i < oks.size(); i++) printf("%s%d", i ? ", " : "", oks[i]);
+  printf("], ");
+  list("u", us);
+  list("k", ks);
+  list("u_plain", up);
+  list("k_plain", kp);
+  printf("\"fp_mul\": {\"key_table\": %llu, \"u_fixed\": %llu, \"p_fixed\": %llu, \"lines1\": %llu, \"f1\": %llu,"
+         " \"final_exp\": %llu, \"lines2\": %llu, \"f2\": %llu}}\n", n_tk, n_u, n_p, n_l1, n_f1, n_fexp, n_l2, n_f2);
+  return table_match && two_pair_match ? 0 : 1;
+}
+
 // The batch path's subgroup check of a decoded sigma (not infinity): the call-free line steps of
 // k_miller_lines over |x|'s bits (the lines themselves dropped; they do not depend on the check) and
 // pairing.h miller_t_in_subgroup on the T they leave. close_muls: the Fp products of that closing test.
@@ -836,6 +957,7 @@ int main(int argc, char** argv) {
   if (argc == 2 && !strcmp(argv[1], "subgroup")) return cmd_subgroup();
   if (argc == 3 && !strcmp(argv[1], "tlock")) return cmd_tlock(argv[2]);
   if (argc == 4 && !strcmp(argv[1], "tseal")) return cmd_tseal(argv[2], strtoull(argv[3], nullptr, 10));
+  if (argc == 3 && !strcmp(argv[1], "tsealr")) return cmd_tsealr(argv[2]);
   if (argc == 4 && !strcmp(argv[1], "rlc")) return cmd_rlc(argv[2], strtoul(argv[3], nullptr, 10));
   if (argc >= 2 && !strcmp(argv[1], "ops")) return cmd_ops(argc == 3 && !strcmp(argv[2], "list"));
   if (argc == 3 && !strcmp(argv[1], "hash")) return cmd_hash(argv[2]);
@@ -848,8 +970,9 @@ int main(int argc, char** argv) {
     fprintf(stderr, "usage: %s pk48hex round prevhex|- sig96hex   (prev '-' = unchained V2)\n       %s hash msghex\n"
             "       %s tlock sig96hex   (one compressed U in hex per line on stdin)\n"
             "       %s subgroup   (one compressed G2 point in hex per line on stdin)\n"
-            "       %s tseal pk48hex round   (one 32-byte scalar in hex per line on stdin)\n",
-            argv[0], argv[0], argv[0], argv[0], argv[0]);
+            "       %s tseal pk48hex round   (one 32-byte scalar in hex per line on stdin)\n"
+            "       %s tsealr pk48hex   (one \"round scalarhex\" per line on stdin)\n",
+            argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
     return 2;
   }
   auto pk = unhex(argv[1]);

@@ -18,6 +18,12 @@ one-item call with a new signature (decode + prepare + one pass) and with the ca
 the result opened, every opened value compared with the sealed one.
 
     python tools/tlock_bench.py --sealed            # writes profiles/tseal_bench.json on an MI355X
+
+--sealed-rounds measures the sealing to many rounds (see sealed_rounds() below): distinct scalars to
+distinct rounds in one call beside the one-round seal and the opening, the 64-round fixed-cost case and
+the crossover against a loop of one-round seals.
+
+    python tools/tlock_bench.py --sealed-rounds     # writes profiles/tseal_rounds_bench.json on an MI355X
 """
 from __future__ import annotations
 
@@ -156,6 +162,169 @@ def sealed(args):
     return 0 if all_sealed and round_trip and distinct_us == n else 1
 
 
+def sealed_rounds(args):
+    """--sealed-rounds: n DISTINCT seeded scalars sealed on the device to n DISTINCT rounds 1..n in one
+    call (Engine.tlock_seal_rounds_dev); beside it, in the same run, the same scalars sealed to the one
+    round 7 (Engine.tlock_seal_dev) and the U values opened with round 7's SignatureV2
+    (Engine.tlock_open_dev). After warm-up, --pairs interleaved repetitions of the three, each timed with
+    a host clock around the call and a device synchronise; medians, and the stage events of one more
+    many-rounds call. Device comparisons: both paths give the same U; the many-rounds call with every
+    round set to 7 gives exactly the opened values; item 6 of the timed call (round 7) does too.
+
+    The fixed-cost case the call exists for: 64 items with 64 distinct rounds as ONE call against 64
+    one-item Engine.tlock_seal_dev calls (each builds a new base), interleaved, new rounds every
+    repetition; the one call must be at least 10 times faster (exit status 1 otherwise), and both give the
+    same bytes. The crossover: 4 rounds with m items each as one many-rounds call against 4 one-round
+    calls, m in powers of 4: the smallest m at which the loop over the rounds wins."""
+    import torch
+
+    from drand_amd.engine import Engine
+
+    if not torch.cuda.is_available():
+        raise SystemExit("tlock_bench needs the GPU: nothing here is measured without one")
+    with open(os.path.join(ROOT, "tests", "golden", "golden.json")) as f:
+        ch = json.load(f)["chained"]
+    sig = {b["round"]: bytes.fromhex(b["sig_v2"]) for b in ch["beacons"]}
+    dev = torch.device("cuda", 0)
+    n, round_ = args.items, 7
+    eng = Engine(0)
+    eng.set_public_key(bytes.fromhex(ch["pk"]))
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(2)
+    scalars = torch.randint(0, 256, (n * 32,), dtype=torch.uint8, device=dev, generator=gen)
+    rounds = torch.arange(1, n + 1, dtype=torch.int64, device=dev)
+    us_r = torch.empty(n * 48, dtype=torch.uint8, device=dev)
+    ks_r = torch.empty(n * 576, dtype=torch.uint8, device=dev)
+    ok_r = torch.empty(n, dtype=torch.uint8, device=dev)
+    us = torch.empty(n * 48, dtype=torch.uint8, device=dev)
+    ks = torch.empty(n * 576, dtype=torch.uint8, device=dev)
+    ok = torch.empty(n, dtype=torch.uint8, device=dev)
+    opened = torch.empty(n * 576, dtype=torch.uint8, device=dev)
+    cls = torch.empty(n, dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize(dev)
+
+    def timed(f):
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        f()
+        eng.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    def seal_rounds(rs=rounds, m=n, at=0):
+        return timed(lambda: eng.tlock_seal_rounds_dev(rs.data_ptr(), scalars.data_ptr() + 32 * at, m,
+                                                       us_r.data_ptr() + 48 * at, ks_r.data_ptr() + 576 * at,
+                                                       ok_r.data_ptr() + at))
+
+    def seal_one(r=round_, m=n, at=0):
+        return timed(lambda: eng.tlock_seal_dev(r, scalars.data_ptr() + 32 * at, m, us.data_ptr() + 48 * at,
+                                                ks.data_ptr() + 576 * at, ok.data_ptr() + at))
+
+    def opening():
+        return timed(lambda: eng.tlock_open_dev(sig[round_], us.data_ptr(), n, opened.data_ptr(), cls.data_ptr()))
+
+    for _ in range(args.warmup):
+        seal_rounds(), seal_one(), opening()
+    rounds_ms, one_ms, open_ms = [], [], []
+    for _ in range(args.pairs):
+        rounds_ms.append(seal_rounds())
+        one_ms.append(seal_one())
+        open_ms.append(opening())
+    all_sealed = int(ok_r.min().item()) == 1 and int(ok.min().item()) == 1 and int(cls.max().item()) == 0
+    same_us = bool(torch.equal(us_r, us))
+    one_equals_open = bool(torch.equal(opened, ks))
+    item_round7 = bool(torch.equal(ks_r.view(n, 576)[round_ - 1], opened.view(n, 576)[round_ - 1])) if n >= round_ else True
+    distinct_ks = int(torch.unique(ks_r.view(n, 576)[:min(n, 65536), :16], dim=0).shape[0])
+    eng.profile(True)
+    eng.profile_read()
+    seal_rounds()
+    st_rounds = {k: round(v[0], 3) for k, v in eng.profile_read().items() if v[1]}
+    eng.profile(False)
+    # every round 7: the many-rounds path must give exactly what the opening gave
+    seal_rounds(torch.full((n,), round_, dtype=torch.int64, device=dev))
+    rounds_equal_open = bool(torch.equal(ks_r, opened))
+
+    # the fixed-cost case: 64 items, 64 distinct rounds
+    m64 = min(64, n)
+    call_ms, loop_ms, fixed_same = [], [], True
+    for rep in range(args.pairs + args.warmup):
+        r0 = 1000 + 64 * rep
+        rs = torch.arange(r0, r0 + m64, dtype=torch.int64, device=dev)
+        a = seal_rounds(rs, m64)
+        torch.cuda.synchronize(dev)
+        t0 = time.perf_counter()
+        for i in range(m64):
+            eng.tlock_seal_dev(r0 + i, scalars.data_ptr() + 32 * i, 1, us.data_ptr() + 48 * i, ks.data_ptr() + 576 * i,
+                               ok.data_ptr() + i)
+        eng.synchronize()
+        b = (time.perf_counter() - t0) * 1e3
+        fixed_same &= bool(torch.equal(ks_r[:576 * m64], ks[:576 * m64]) and torch.equal(us_r[:48 * m64], us[:48 * m64]))
+        if rep >= args.warmup:
+            call_ms.append(a)
+            loop_ms.append(b)
+    fixed_ratio = statistics.median(loop_ms) / statistics.median(call_ms)
+
+    # the crossover: R rounds x m items
+    R, cross, table = 4, None, []
+    m = 1
+    while R * m <= n:
+        rs = (torch.arange(R * m, dtype=torch.int64, device=dev) % R) + 5000
+        a, b = [], []
+        for rep in range(3):
+            a.append(seal_rounds(rs, R * m))
+            t = 0.0
+            for j in range(R):
+                t += seal_one(6000 + 8 * rep + j + 100 * len(table), m, j * m)
+            b.append(t)
+        table.append({"items_per_round": m, "one_call_ms": round(statistics.median(a), 3),
+                      "loop_ms": round(statistics.median(b), 3)})
+        if cross is None and statistics.median(b) < statistics.median(a):
+            cross = m
+        m *= 4
+
+    mr, ms, mo = statistics.median(rounds_ms), statistics.median(one_ms), statistics.median(open_ms)
+    counts = json.load(open(os.path.join(ROOT, "profiles", "tsealr_opcount.json")))
+    hash_mul = json.load(open(os.path.join(ROOT, "profiles", "opcount.json")))["fp_mul"]["hash"]
+    one_counts = json.load(open(os.path.join(ROOT, "profiles", "tseal_opcount.json")))["fp_mul"]
+    opening_counts = json.load(open(os.path.join(ROOT, "profiles", "tlock_opcount.json")))["fp_mul"]
+    per_item = counts["per_item_without_hash"] + hash_mul
+    res = {"tool": "tools/tlock_bench.py --sealed-rounds", "items": n, "distinct_rounds": n, "distinct_scalars": n,
+           "distinct_k_prefixes_of_first_64ki": distinct_ks, "pairs": args.pairs, "warmup": args.warmup,
+           "device": torch.cuda.get_device_name(0),
+           "timing": "host clock around the call and a device synchronise; device-resident inputs and outputs",
+           "seal_rounds_ms": [round(x, 2) for x in rounds_ms], "seal_one_round_ms": [round(x, 2) for x in one_ms],
+           "open_ms": [round(x, 2) for x in open_ms],
+           "seal_rounds_ms_median": round(mr, 2), "seal_one_round_ms_median": round(ms, 2), "open_ms_median": round(mo, 2),
+           "seals_per_s_many_rounds": round(n / (mr / 1e3)), "seals_per_s_one_round": round(n / (ms / 1e3)),
+           "opens_per_s": round(n / (mo / 1e3)),
+           "stage_ms_seal_rounds": st_rounds,
+           "fp_products_per_item": {"many_rounds": per_item, "one_round": one_counts["u_fixed"] + one_counts["gt_fixed"],
+                                    "opening": opening_counts["tlock_f"] + opening_counts["final_exp"]},
+           "many_rounds_over_open_measured": round(mr / mo, 3),
+           "many_rounds_over_open_predicted_by_fp_products": round(
+               per_item / (opening_counts["tlock_f"] + opening_counts["final_exp"]), 3),
+           "fixed_cost_64_rounds": {"items": m64, "one_call_ms": [round(x, 3) for x in call_ms],
+                                    "loop_of_one_item_seals_ms": [round(x, 3) for x in loop_ms],
+                                    "one_call_ms_median": round(statistics.median(call_ms), 3),
+                                    "loop_ms_median": round(statistics.median(loop_ms), 3),
+                                    "speedup": round(fixed_ratio, 2), "required": 10, "same_bytes": fixed_same},
+           "crossover": {"rounds": R, "table": table, "loop_wins_from_items_per_round": cross},
+           "all_sealed": all_sealed, "same_us_on_both_paths": same_us, "one_round_equals_open": one_equals_open,
+           "round7_item_equals_open": item_round7, "all_round7_equals_open": rounds_equal_open,
+           "tlock_seal_rounds_stats": eng.tlock_seal_rounds_stats(), "tlock_seal_stats": eng.tlock_seal_stats(),
+           "tlock_stats": eng.tlock_stats()}
+    on_mi355x = "gfx950" in getattr(torch.cuda.get_device_properties(0), "gcnArchName", "")
+    out = args.out or (os.path.join(ROOT, "profiles", "tseal_rounds_bench.json") if on_mi355x else None)
+    if out:
+        with open(out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+    print(json.dumps(res))
+    eng.close()
+    good = (all_sealed and same_us and one_equals_open and item_round7 and rounds_equal_open and fixed_same
+            and fixed_ratio >= 10)
+    return 0 if good else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--items", type=int, default=1 << 20)
@@ -166,9 +335,14 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--sealed", action="store_true",
                     help="seal --items distinct scalars on the device and open the result (profiles/tseal_bench.json)")
+    ap.add_argument("--sealed-rounds", action="store_true",
+                    help="seal --items scalars to --items distinct rounds in one call, beside the one-round seal and "
+                         "the opening (profiles/tseal_rounds_bench.json)")
     args = ap.parse_args()
     if args.sealed:
         return sealed(args)
+    if args.sealed_rounds:
+        return sealed_rounds(args)
 
     import numpy as np
     import torch
