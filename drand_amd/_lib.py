@@ -32,6 +32,7 @@ REJ_NOT_ON_CURVE = 5
 REJ_NOT_IN_SUBGROUP = 6
 REJ_PAIRING = 7
 REJ_SHARE_INDEX = 8
+REJ_TLOCK_SIG = 9
 
 REJ_NAMES = {
     REJ_OK: "ok",
@@ -43,6 +44,7 @@ REJ_NAMES = {
     REJ_NOT_IN_SUBGROUP: "point is not on correct subgroup",
     REJ_PAIRING: "bls: invalid signature",
     REJ_SHARE_INDEX: "tbls: invalid signature share",
+    REJ_TLOCK_SIG: "timelock: the round signature did not decode",
 }
 
 u8p = ctypes.POINTER(ctypes.c_uint8)
@@ -111,6 +113,10 @@ SIGNATURES = {
     "blsv_tlock_open": (ctypes.c_int, [vp, u8p, u8p, sz, u8p, u8p, u8p, u8p]),
     "blsv_tlock_open_dev": (ctypes.c_int, [vp, u8p, vp, sz, vp, vp, vp]),
     "blsv_tlock_stats": (ctypes.c_int, [vp, u64p, u64p]),
+    "blsv_tlock_open_rounds": (ctypes.c_int, [vp, u8p, u64p, sz, u8p, sz, u8p, u8p, u8p, u8p]),
+    "blsv_tlock_open_rounds_dev": (ctypes.c_int, [vp, u8p, u64p, sz, vp, sz, vp, vp, vp, vp]),
+    "blsv_tlock_open_rounds_stats": (ctypes.c_int, [vp, u64p, u64p]),
+    "blsv_set_tlock_dense_min": (sz, [vp, sz]),
     "blsv_tlock_seal": (ctypes.c_int, [vp, u8p, ctypes.c_uint64, u8p, sz, u8p, u8p, u8p]),
     "blsv_tlock_seal_dev": (ctypes.c_int, [vp, u8p, ctypes.c_uint64, vp, sz, vp, vp, vp, vp]),
     "blsv_tlock_seal_stats": (ctypes.c_int, [vp, u64p, u64p]),

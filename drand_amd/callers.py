@@ -336,6 +336,50 @@ def timelock_open(engine, round_: int, sig_v2: bytes, ciphertexts, kdf: Callable
     return out
 
 
+def timelock_open_rounds(engine, rounds, kdf: Callable[[bytes, int], bytes], verify: bool = True) -> list:
+    """Opens the ciphertexts of MANY rounds in ONE engine call (``Engine.tlock_open_rounds``): the shape
+    of a vault back from downtime or an auditor opening a day of rounds. ``rounds`` is a sequence of
+    ``(round, sig_v2, [(U48, C), ...])``; returns one list per round, each what
+    ``timelock_open(engine, round, sig_v2, ciphertexts, kdf)`` gives: ``C XOR kdf(gt_i, len(C))`` per
+    ciphertext, or ``None`` where U did not decode (a wrong-length U is filtered host-side).
+
+    ``verify=True`` first checks all the signatures in one ``verify_unchained(sigs, rounds=...)`` under
+    the engine's group key and raises ``VerifyError`` for the first rejected round before anything is
+    opened. With ``verify=False`` a signature that does not even decode opens nothing: every ciphertext
+    of its round is ``None``."""
+    rounds = [(int(r), bytes(s), [(bytes(u), bytes(c)) for u, c in cts]) for r, s, cts in rounds]
+    if verify:
+        from ._lib import REJ_NAMES
+        for r, s, _ in rounds:
+            if len(s) != SIG_LEN:
+                raise VerifyError(r, "bad length")
+        if rounds:
+            res = engine.verify_unchained([s for _, s, _ in rounds], rounds=[r for r, _, _ in rounds])
+            for (r, _, _), ok, cls in zip(rounds, res.ok, res.reject_class):
+                if not ok:
+                    raise VerifyError(r, REJ_NAMES.get(cls, "bls: invalid signature"))
+    good = [[k for k, (u, _) in enumerate(cts) if len(u) == 48] for _, _, cts in rounds]
+    res = engine.tlock_open_rounds([s for _, s, _ in rounds],
+                                   [[cts[k][0] for k in g] for (_, _, cts), g in zip(rounds, good)])
+    out, at = [], 0
+    for (_, _, cts), g in zip(rounds, good):
+        gts = [None] * len(cts)
+        for k in g:
+            gts[k] = res.gt[at]
+            at += 1
+        opened = []
+        for (_, c), gt in zip(cts, gts):
+            if gt is None:
+                opened.append(None)
+                continue
+            ks = kdf(gt, len(c))
+            if len(ks) != len(c):
+                raise ValueError("kdf returned %d bytes for a %d-byte ciphertext" % (len(ks), len(c)))
+            opened.append(bytes(a ^ b for a, b in zip(c, ks)))
+        out.append(opened)
+    return out
+
+
 def timelock_seal(engine, round_: int, messages, kdf: Callable[[bytes, int], bytes], scalars=None, pk48=None) -> list:
     """Locks every message to ``round_`` in ONE engine call (``Engine.tlock_seal``): returns a list of
     ``(U48, C)`` with ``U = k G1`` and ``C = m XOR kdf(gt, len(m))``, ``gt`` the 576-byte encoding of

@@ -1,5 +1,5 @@
 // Internal to libblsverify.so (never installed, no C ABI): the context object and the helpers the
-// C-ABI entry points (blsverify.cpp, verify.cpp, threshold.cpp, tlock.cpp, tseal.cpp, tsealr.cpp, testhooks.cpp; their shared
+// C-ABI entry points (blsverify.cpp, verify.cpp, threshold.cpp, tlock.cpp, tlockr.cpp, tseal.cpp, tsealr.cpp, testhooks.cpp; their shared
 // internals are host_internal.h) and the thread-safe service (service.cpp) share.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/blsverify.h"
+#include "hostlogic.h"
 #include "kernels.h"
 
 namespace blsv_detail {
@@ -107,6 +108,29 @@ static_assert(96 == 4 * blsk::G1_WORDS && (96 + BLSV_SCALAR_LEN) % 8 == 0,
 static_assert(blsk::kMillerLine1Words <= blsk::MILLER_LINE_WORDS &&
                   blsk::FEXP_PARK_WORDS(kMaxChunk) <= blsk::MILLER_LINE_WORDS * kMaxChunk,
               "sealing to many rounds: the single-pair lines, then the park, do not fit LN");
+
+// Timelock opening across many rounds (blsv_tlock_open_rounds*, tlockr.cpp, tlockr.h) runs in the same
+// staging with the plan of a one-signature opening, plus what its many signatures need. A pass of cnt items
+// that touches M <= cnt signatures with items:
+//   S          a host call's compressed U bytes until launch_decompress_g1 has read them; then the M
+//              decoded signatures (SoA of stride M), read by k_tlock_prepare_many
+//   H, h_inf   the decoded U table with its flags; s_inf: the items' class bytes (the f pass adds
+//              BLSV_REJ_TLOCK_SIG); cls: their copy for the final exponentiation, taken behind the f pass
+//   LN         the word-major table of the M signatures (kTlockTabWords words each: the first half of LN
+//              at most) until the f pass has read it; then the final exponentiation's park, as in an opening
+//   FW         until the final exponentiation takes it as scratch (hostlogic.h open_rounds_layout, 22 bytes
+//              per item of the workspace): the signatures' class and infinity bytes, and the host's plan
+//              of the pass -- sig_j, sig_of and the tiles
+//   F, HQ      as in a timelock opening: f, the captured E_i; a host call's encoded bytes back in F
+// The pass's compressed signatures travel in in_sigs, and a host call's m class bytes wait in misc for one
+// download at the end. Signatures of rounds without items are decoded in batches of their own (S, FW).
+// No table outlives its pass; the only storage of its own is the 8-byte counter of prepared signatures.
+static_assert(2 * blsk::kTlockTabWords <= blsk::MILLER_LINE_WORDS,
+              "opening across rounds: the tables of a pass's signatures (at most one per item) exceed half of LN");
+static_assert(blsk::FEXP_PARK_WORDS(kMaxChunk) <= blsk::MILLER_LINE_WORDS * kMaxChunk,
+              "opening across rounds: the park does not fit LN behind the f pass");
+static_assert(2 + 4 + 4 + 4 * blsk::kTlockTileWords <= 4 * 3 * blsk::F_WORDS,
+              "opening across rounds: the signatures' flags and the plan of a pass do not fit the FW staging");
 
 struct DBuf {
   void* p = nullptr;
@@ -274,6 +298,15 @@ struct tsealr_state {
   DBuf tk;
 };
 
+// Timelock opening across many rounds (blsv_tlock_open_rounds*): no cache. dense_min: the shortest run
+// that gets uniform tiles (blsv_set_tlock_dense_min; hostlogic.h kTlockDenseMinDefault); prepared: the
+// device counter k_tlock_prepare_many adds to (a device call reads no class back, so the host cannot count).
+struct tlockr_state {
+  size_t dense_min = kTlockDenseMinDefault;
+  uint64_t items = 0;  // blsv_tlock_open_rounds_stats
+  DBuf prepared;
+};
+
 struct blsv_ctx {
   int device = 0;
   bool prof = false;
@@ -338,6 +371,7 @@ struct blsv_ctx {
   tlock_state tlock;
   tseal_state tseal;
   tsealr_state tsealr;
+  tlockr_state tlockr;
 };
 
 #define HIPCHK(ctx, expr)                                                             \

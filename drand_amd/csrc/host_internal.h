@@ -1,5 +1,5 @@
 // Internal to the HIP-side host units of libblsverify.so (blsverify.cpp, verify.cpp, threshold.cpp,
-// tlock.cpp, tseal.cpp, tsealr.cpp, testhooks.cpp): the pinned small copies, stage timing, the typed view of the pipeline
+// tlock.cpp, tlockr.cpp, tseal.cpp, tsealr.cpp, testhooks.cpp): the pinned small copies, stage timing, the typed view of the pipeline
 // staging with its launch wrappers, and the one pass loop every verification entry point runs.
 #pragma once
 #include <functional>

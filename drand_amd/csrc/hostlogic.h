@@ -298,5 +298,110 @@ inline SealRoundsLayout seal_rounds_layout(size_t cnt) {
   return l;
 }
 
+// ---------------------------------------------------------------- blsv_tlock_open_rounds*: the plan
+// m round signatures, round j owning counts[j] consecutive items of the n packed ones. Whether the call's
+// arguments are consistent and every byte count of it fits size_t: sum counts == n (the sum itself must
+// not wrap), n x 576 and m x 96 fit, and a signature index fits the uint32 the tiles carry.
+inline bool open_rounds_fits(const uint64_t* counts, size_t m, size_t n) {
+  if (n > SIZE_MAX / BLSV_GT_LEN || m > SIZE_MAX / 96 || m >= UINT32_MAX) return false;
+  uint64_t sum = 0;
+  for (size_t j = 0; j < m; j++) {
+    if (counts[j] > (uint64_t)n - sum) return false;  // sum <= n holds, so the difference does not wrap
+    sum += counts[j];
+  }
+  return sum == n;
+}
+
+// The f pass runs one one-wave workgroup per tile: up to 64 consecutive items of the pass that share
+// signature `sig` (an index into the pass's own signature list), or, with sig == kTlockTileMixed, items of
+// several short runs whose lanes look their signature up per item.
+constexpr uint32_t kTlockTileMixed = 0xffffffffu;
+constexpr size_t kTlockTileItems = 64;
+// A run of at least this many items gets uniform tiles (blsv_set_tlock_dense_min). The measured crossover
+// (profiles/topen_rounds_bench.json; 1 Mi items, ms all-uniform / all-mixed): runs of 16
+// 582.9 / 296.2, 32 389.4 / 293.7, 64 293.4 / 293.2, 128 293.6 / 293.4 -- below a full wave a uniform tile
+// idles lanes and loses outright; from a full wave on the two forms are within the run-to-run spread, so
+// uniform wins at no run length of the sweep and the default is the end of the swept range, not 64.
+constexpr size_t kTlockDenseMinDefault = 128;
+struct TlockTile {
+  uint32_t first, len, sig;
+};
+// One pass: the items [base, base + cnt) of the call, cnt <= cap. sig_j: the call's index of every
+// signature with items in the pass, ascending (at most cnt of them; zero-count rounds are not listed);
+// sig_of[i]: the position in sig_j of item i's signature; tiles: every item of the pass exactly once, in
+// order.
+struct TlockRoundsPass {
+  size_t base = 0, cnt = 0;
+  std::vector<uint32_t> sig_j, sig_of;
+  std::vector<TlockTile> tiles;
+};
+struct TlockRoundsCursor {
+  size_t j = 0;       // the round the next pass starts in
+  uint64_t used = 0;  // items of round j that earlier passes took
+  size_t base = 0;
+};
+// The next pass of at most cap items, or false when no item is left. The rounds are walked in order; the
+// part of a run that lies in this pass (a run cut by the pass boundary is prepared in both passes) becomes
+// uniform tiles when it has at least dense_min items, and the stretches of shorter parts between them are
+// cut into mixed tiles. dense_min = 1: every tile uniform; SIZE_MAX: every tile mixed.
+inline bool open_rounds_next_pass(const uint64_t* counts, size_t m, size_t cap, size_t dense_min, TlockRoundsCursor& cur,
+                                  TlockRoundsPass& p) {
+  p.base = cur.base;
+  p.cnt = 0;
+  p.sig_j.clear();
+  p.sig_of.clear();
+  p.tiles.clear();
+  size_t mixed_from = 0;  // the open stretch of short runs is [mixed_from, p.cnt)
+  auto cut = [&](size_t from, size_t to, uint32_t sig) {
+    for (size_t f = from; f < to; f += kTlockTileItems)
+      p.tiles.push_back({(uint32_t)f, (uint32_t)std::min(kTlockTileItems, to - f), sig});
+  };
+  while (cur.j < m && p.cnt < cap) {
+    const uint64_t left = counts[cur.j] - cur.used;
+    if (left == 0) {
+      cur.j++;
+      cur.used = 0;
+      continue;
+    }
+    const size_t take = (size_t)std::min<uint64_t>(left, cap - p.cnt);
+    const uint32_t sig = (uint32_t)p.sig_j.size();
+    p.sig_j.push_back((uint32_t)cur.j);
+    p.sig_of.insert(p.sig_of.end(), take, sig);
+    if (take >= dense_min) {
+      cut(mixed_from, p.cnt, kTlockTileMixed);
+      cut(p.cnt, p.cnt + take, sig);
+      mixed_from = p.cnt + take;
+    }
+    p.cnt += take;
+    cur.used += take;
+    if (cur.used == counts[cur.j]) {
+      cur.j++;
+      cur.used = 0;
+    }
+  }
+  cut(mixed_from, p.cnt, kTlockTileMixed);
+  cur.base += p.cnt;
+  return p.cnt != 0;
+}
+
+// What a pass keeps in the FW staging until its f pass has run (the final exponentiation then takes FW as
+// its scratch), for a workspace of cap items (a multiple of 64): the class and infinity bytes of the
+// pass's decoded signatures, then the three arrays the host uploads in one copy -- sig_j, sig_of and the
+// tiles (at most one of each per item).
+struct OpenRoundsLayout {
+  size_t o_cls, o_inf, o_sigj, o_sigof, o_tiles, total;
+};
+inline OpenRoundsLayout open_rounds_layout(size_t cap) {
+  OpenRoundsLayout l;
+  l.o_cls = 0;
+  l.o_inf = cap;
+  l.o_sigj = 2 * cap;
+  l.o_sigof = l.o_sigj + 4 * cap;
+  l.o_tiles = l.o_sigof + 4 * cap;
+  l.total = l.o_tiles + sizeof(TlockTile) * cap;
+  return l;
+}
+constexpr size_t kOpenRoundsFwBytesPerItem = 2 + 4 + 4 + sizeof(TlockTile);
+
 }  // namespace blsv_detail
 #pragma GCC visibility pop

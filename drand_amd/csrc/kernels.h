@@ -118,6 +118,26 @@ void launch_tlock_f(const uint32_t* tab, const uint32_t* U, const uint8_t* u_inf
                     const uint8_t* sig_inf, size_t cnt, uint32_t* F, hipStream_t st);
 void launch_tlock_encode(const uint32_t* E, const uint8_t* cls, size_t cnt, uint8_t* out, hipStream_t st);
 
+// ---- timelock opening across many rounds (k_tlockr.hip, tlockr.h): E_i = e(U_i, sigma_j)^3, round j owning a
+// run of consecutive items. prepare_many: the staging launch_decompress_g2 filled for the pass's M
+// signatures (stride M) -> tab, kTlockTabWords x M words, word w of signature j at tab[w * M + j] (a column
+// is untouched when its sigma did not decode or is the point at infinity); *prepared += the sigmas that
+// decoded. f_tiles: one one-wave workgroup per tile of kTlockTileWords words (first item, length <= 64,
+// signature index < M or kTlockTileMixed), the n_uniform uniform tiles first and the n_mixed mixed ones
+// behind them; sig_of[i] = item i's signature index (read by mixed tiles); U / u_inf / cls as
+// launch_decompress_g1 wrote them for cnt items -> F as launch_tlock_f leaves it, and cls[i] = 9
+// (BLSV_REJ_TLOCK_SIG) where cls[i] was 0 and the item's sigma did not decode. scatter_classes:
+// dst[sig_j[k]] = src[k] for k < M.
+constexpr uint32_t kTlockTileMixed = 0xffffffffu;
+constexpr size_t kTlockTileWords = 3;
+void launch_tlock_prepare_many(const uint32_t* S, const uint8_t* s_inf, const uint8_t* s_cls, size_t M, uint32_t* tab,
+                               unsigned long long* prepared, hipStream_t st);
+void launch_tlock_f_tiles(const uint32_t* tiles, size_t n_uniform, size_t n_mixed, const uint32_t* sig_of,
+                          const uint32_t* tab, size_t M, const uint8_t* sig_inf, const uint8_t* sig_cls,
+                          const uint32_t* U, const uint8_t* u_inf, uint8_t* cls, size_t cnt, uint32_t* F,
+                          hipStream_t st);
+void launch_tlock_scatter_classes(const uint8_t* src, const uint32_t* sig_j, size_t M, uint8_t* dst, hipStream_t st);
+
 // ---- timelock sealing (k_tseal.hip, tseal.h): U_i = k_i G1, K_i = B^k_i under one shared base B.
 // g1_table: T1 (kTsealT1Words words), the multiples j 16^w G1. gt_table: B = the base's Fp12 (144 words,
 // Montgomery, tower order: a captured final-exponentiation value of stride 1) -> T2 (kTsealT2Words words),

@@ -54,6 +54,16 @@ class TlockResult:
     gt: list
 
 
+@dataclass
+class TlockRoundsResult:
+    """Outcome of Engine.tlock_open_rounds: ok, reject_class and gt per item in packed order (as
+    TlockResult's), sig_class[j] per round signature (0 = decoded)."""
+    ok: list
+    reject_class: list
+    gt: list
+    sig_class: list
+
+
 # the order r of G1 / G2 / Gt: sealing scalars are taken mod r
 R_ORDER = 0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001
 
@@ -438,6 +448,58 @@ class Engine:
         a, b = ctypes.c_uint64(), ctypes.c_uint64()
         self._check(self.lib.blsv_tlock_stats(self._h, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value
+
+    # ------------------------------------------------------------------ timelock opening across many rounds
+    # include/blsverify.h "timelock": m round signatures, round j owning a run of consecutive U values;
+    # every item is what tlock_open(sigs[j], [U_i]) gives. Nothing is cached.
+    @staticmethod
+    def _rounds_args(sigs, counts):
+        sigs = [bytes(s) for s in sigs]
+        counts = [int(k) for k in counts]
+        if any(len(s) != 96 for s in sigs):
+            raise ValueError("a round signature is 96 bytes")
+        if len(counts) != len(sigs) or any(not 0 <= k < 1 << 64 for k in counts):
+            raise ValueError("one uint64 count per round signature")
+        m = len(sigs)
+        return _lib.buf(b"".join(sigs)), (ctypes.c_uint64 * max(m, 1))(*counts), m
+
+    def tlock_open_rounds(self, sigs, us_per_round):
+        """blsv_tlock_open_rounds: `sigs` are m 96-byte round signatures and `us_per_round` m sequences of
+        compressed G1 points (round j's ciphertexts; an empty one is allowed). Returns
+        TlockRoundsResult(ok, reject_class, gt, sig_class): ok, reject_class and gt in packed order (round
+        0's items, then round 1's, ...), gt[i] 576 bytes or None where the item did not open; sig_class[j]
+        = REJ_* of a signature that did not decode (its items have class REJ_TLOCK_SIG unless their own U
+        is rejected) and 0 otherwise. The signatures are NOT verified here."""
+        runs = [[bytes(u) for u in run] for run in us_per_round]
+        us = [u for run in runs for u in run]
+        if any(len(u) != 48 for u in us):
+            raise ValueError("U values must be 48 bytes (reject wrong lengths host-side)")
+        sb, counts, m = self._rounds_args(sigs, [len(run) for run in runs])
+        n = len(us)
+        out, ok, cls, sc = _lib.out_buf(n * 576), _lib.out_buf(n), _lib.out_buf(n), _lib.out_buf(m)
+        self._check(self.lib.blsv_tlock_open_rounds(self._h, sb, counts, m, _lib.buf(b"".join(us)), n, out, ok, cls, sc))
+        ob = bytes(out)
+        oks = [bool(x) for x in list(ok)[:n]]
+        return TlockRoundsResult(oks, list(cls)[:n], [ob[576 * i:576 * i + 576] if oks[i] else None for i in range(n)],
+                                 list(sc)[:m])
+
+    def tlock_open_rounds_dev(self, sigs, counts, d_us, n, d_out, d_cls=None, d_sig_cls=None, stream=None):
+        """blsv_tlock_open_rounds_dev: `sigs` and `counts` (host: m signatures, m item counts summing to n)
+        over n device-resident U values -> n x 576 bytes at d_out (4-byte aligned), optional class bytes at
+        d_cls (n) and d_sig_cls (m); asynchronous on `stream`, no class is read back."""
+        sb, cn, m = self._rounds_args(sigs, counts)
+        self._check(self.lib.blsv_tlock_open_rounds_dev(self._h, sb, cn, m, d_us, n, d_out, d_cls, d_sig_cls, stream))
+
+    def tlock_open_rounds_stats(self):
+        """(signatures prepared, U values processed) by tlock_open_rounds* since the context was created."""
+        a, b = ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(self.lib.blsv_tlock_open_rounds_stats(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
+
+    def set_tlock_dense_min(self, items):
+        """blsv_set_tlock_dense_min: the shortest run that gets uniform tiles in tlock_open_rounds* (1 = every
+        tile uniform, 2^64 - 1 = every tile mixed, 0 = the default); returns the previous value."""
+        return int(self.lib.blsv_set_tlock_dense_min(self._h, int(items)))
 
     # ------------------------------------------------------------------ timelock sealing
     # include/blsverify.h "timelock": U_i = k_i G1 and K_i = B^k_i with B = e(pk, H(MessageV2(round)))^3

@@ -401,6 +401,68 @@ int blsv_tlock_open_dev(blsv_ctx* ctx, const uint8_t* sig96, const uint8_t* d_us
 int blsv_tlock_stats(blsv_ctx* ctx, uint64_t* prepared, uint64_t* items);
 
 /*
+ * Opening across many rounds: the mirror image of blsv_tlock_seal_rounds below. A vault that comes back
+ * after downtime, an auditor who opens a day of a 3-second chain (28,800 rounds), an auction whose bids
+ * were locked to a spread of rounds: each holds ciphertexts for many rounds at once, usually a few per
+ * round. blsv_tlock_open_rounds opens them in ONE call instead of one blsv_tlock_open per round.
+ *
+ * Inputs
+ *  - sigs96: m round signatures (96 bytes each), counts: m item counts. Round j owns counts[j] ciphertexts;
+ *    the U values of round 0, round 1, ... are packed back to back in us48 (the convention of msgs /
+ *    msg_lens in blsv_verify_messages). sum counts must equal n and m must be below 2^32: anything else,
+ *    or a byte count that would overflow, is BLSV_EINVAL and no output is touched. A count of 0 is allowed;
+ *    that signature is still decoded and classed.
+ *  - Per item: for item i of round j whose sigma_j decodes, the BLSV_GT_LEN output bytes, ok[i] and
+ *    reject_class[i] are byte for byte what blsv_tlock_open(ctx, sigs96 + 96 j, us48 + 48 i, 1, ...)
+ *    returns, E = 1 with ok = 1 for U_i or sigma_j at infinity included.
+ *  - Per signature: a sigma_j that does not decode gets its BLSV_REJ_* class (2-6) in sig_class[j]
+ *    (optional, m bytes; 0 = decoded) and the call still returns BLSV_OK. Every item of round j then has
+ *    ok = 0 and BLSV_GT_LEN zero bytes; its class is U_i's own decode class where that is not 0 (what the
+ *    item would get under any signature), else BLSV_REJ_TLOCK_SIG. The other rounds are unaffected.
+ *  - As blsv_tlock_open, the call does NOT check that sigma_j is round j's signature (it never learns the
+ *    round numbers): verify the m signatures first, in one blsv_verify_unchained.
+ *
+ * State: no cache. The prepared tables (19,584 bytes per signature) live in the pipeline staging for the
+ * duration of a pass. The one-entry sigma cache of blsv_tlock_open, the sealing caches and all their
+ * counters are left alone. blsv_tlock_open_rounds_stats: *prepared = signatures prepared (each sigma that
+ * decodes and has count > 0, once per pass that touches it), *items = U values processed; either pointer
+ * may be NULL. *prepared is kept on the device and read back here (one synchronisation of the context's
+ * stream).
+ *
+ * Sizing: the pipeline staging is used as it is; more than a chunk of items runs in chunk-sized passes
+ * with identical outputs (a round whose run straddles a pass boundary is prepared in both passes).
+ *
+ * How a pass runs: one one-wave workgroup per tile of up to 64 consecutive items. A run of at least
+ * dense_min items gets uniform tiles (all lanes share sigma_j: its table is read from LDS by broadcast, as
+ * blsv_tlock_open reads it); the stretches of shorter runs between them are cut into mixed tiles whose
+ * lanes each read their own signature's table from global memory. Both forms give the same bytes.
+ * blsv_set_tlock_dense_min sets dense_min and returns the previous value: 1 makes every tile uniform,
+ * SIZE_MAX every tile mixed, 0 restores the default. The default is 128, the end of the measured sweep
+ * (run lengths 1 .. 128 at 1 Mi items): below a full wave of 64 a uniform tile idles lanes and loses
+ * outright (16 per run: 582.9 ms against 296.2; 32: 389.4 against 293.7), and at 64 and 128 the two forms are equal within
+ * the run-to-run spread (293.4 against 293.2, 293.6 against 293.4), so uniform wins at no run length up to 128.
+ *
+ * Measured on one MI355X (profiles/topen_rounds_bench.json): 64 items of 64 distinct rounds
+ * take 16.8 ms in one call against 1,206 ms as 64 blsv_tlock_open calls (72 times faster); 1 Mi
+ * distinct U values open at 3.56 M/s under 1 round, 3.57 M/s over 1 Ki rounds, 3.55 M/s over 32 Ki rounds and
+ * 2.88 M/s over 1 Mi rounds, beside 3.64 M/s for blsv_tlock_open_dev on the one-round inputs in the same run.
+ *
+ * blsv_tlock_open_rounds_dev: sigs96 and counts are host memory (as sig96 of blsv_tlock_open_dev);
+ * d_us48 / d_out_gt576 (4-byte aligned) / d_reject_class (optional, n) / d_sig_class (optional, m) are
+ * device pointers. Asynchronous on `stream` under the single-stream rule of blsv_verify_chained_dev; no
+ * class is read back.
+ */
+#define BLSV_REJ_TLOCK_SIG 9 /* the item's round signature did not decode (its class is in sig_class[j]) */
+int blsv_tlock_open_rounds(blsv_ctx* ctx, const uint8_t* sigs96, const uint64_t* counts, size_t m,
+                           const uint8_t* us48, size_t n, uint8_t* out_gt576, uint8_t* ok,
+                           uint8_t* reject_class /*optional, n*/, uint8_t* sig_class /*optional, m*/);
+int blsv_tlock_open_rounds_dev(blsv_ctx* ctx, const uint8_t* sigs96, const uint64_t* counts, size_t m,
+                               const uint8_t* d_us48, size_t n, uint8_t* d_out_gt576,
+                               uint8_t* d_reject_class /*optional*/, uint8_t* d_sig_class /*optional*/, void* stream);
+int blsv_tlock_open_rounds_stats(blsv_ctx* ctx, uint64_t* prepared, uint64_t* items);
+size_t blsv_set_tlock_dense_min(blsv_ctx* ctx, size_t items); /* returns the previous value */
+
+/*
  * Sealing: the producing half, timelock.Encrypt(key.Pairing, G1 base, group key, MessageV2(round), msg)
  * of the same test, for n messages locked to ONE round. With B = e(pk, H(MessageV2(round)))^3 computed
  * once, item i is

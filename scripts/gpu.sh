@@ -19,6 +19,7 @@
 #   intrate          tools/intrate (peak v_mad_u64_u32 rate) and its SQ/GRBM counters (clock of the peak)
 #   lat              tools/latency_bench.py (lone verify, fused round)
 #   latsweep         the same with the latency-vs-batch sweep (64 .. 2048 items: co-resident teams)
+#   topen            tools/topen_rounds_bench.py (timelock opening across many rounds: sweep, loop, crossover)
 #   cfg              tools/config_bench.py (configs[2], configs[4], partials, drand.db)
 #   variant:NAME     GPU suite + bench on variants/libblsverify_NAME.so (scripts/build_variant.sh,
 #                    loaded through DRAND_AMD_LIB)
@@ -87,6 +88,9 @@ for step in "$@"; do
     latsweep)
       timeout -k 10 400 python -u tools/latency_bench.py --reps 5 --sweep 64,256,512,1024,2048 \
         --out "$O/latency_sweep.json" > "$O/latency_sweep.log" 2>&1 || rc=24 ;;
+    topen)
+      timeout -k 10 560 python -u tools/topen_rounds_bench.py --out "$O/topen_rounds_bench.json" \
+        > "$O/topen_rounds_bench.log" 2>&1 || rc=26 ;;
     cfg) timeout -k 10 600 python -u tools/config_bench.py > "$O/config_bench.json" 2> "$O/config_bench.log" || rc=22 ;;
     variant:*)
       V=${step#variant:}

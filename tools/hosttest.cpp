@@ -370,6 +370,68 @@ int test_hostlogic() {
              std::to_string(l.total) + ", " + std::to_string(l.secret) + "]";
     }
   }
+  out += "]}, \"open_rounds\": {\"fits\": [";
+  {
+    // blsv_tlock_open_rounds*: the guard on (counts, m, n) -- the sum must be n without wrapping, and
+    // n x 576 must fit -- then the plan of every pass: each case prints its passes as
+    // [base, cnt, sig_j, tiles] with a tile [first, len, sig] (sig -1 = mixed)
+    const size_t lim = SIZE_MAX / BLSV_GT_LEN;
+    struct Fit {
+      std::vector<uint64_t> counts;
+      size_t n;
+    };
+    const std::vector<Fit> fits = {{{}, 0},          {{1, 2, 3}, 6},       {{1, 2, 3}, 5},          {{1, 2, 3}, 7},
+                                   {{0, 0}, 0},      {{UINT64_MAX, 2}, 1}, {{lim + 1}, lim + 1},    {{}, 1},
+                                   {{4, UINT64_MAX - 3, 4}, 4}};
+    for (size_t k = 0; k < fits.size(); k++) {
+      std::vector<uint64_t> cn(fits[k].counts);  // heap, at the caller's size
+      out += std::string(k ? ", " : "") + (open_rounds_fits(cn.data(), cn.size(), fits[k].n) ? "true" : "false");
+    }
+    out += "], \"plans\": [";
+    struct Plan {
+      std::vector<uint64_t> counts;
+      size_t cap, dense_min;
+    };
+    const std::vector<uint64_t> runs = {0, 1, 63, 0, 64, 65, 129, 0};
+    const std::vector<Plan> plans = {{runs, 1024, 1},       {runs, 1024, 64}, {runs, 1024, SIZE_MAX}, {{100, 60, 3}, 128, 64},
+                                     {{0, 0, 0}, 64, 64},   {{200}, 64, 64},  {{1, 1, 1, 1, 1}, 64, 2}};
+    for (size_t k = 0; k < plans.size(); k++) {
+      std::vector<uint64_t> cn(plans[k].counts);
+      size_t n = 0;
+      for (uint64_t v : cn) n += (size_t)v;
+      std::vector<int> covered(n, 0);
+      std::vector<size_t> owner;  // the round of every item
+      for (size_t j = 0; j < cn.size(); j++) owner.insert(owner.end(), (size_t)cn[j], j);
+      TlockRoundsCursor cur;
+      TlockRoundsPass p;
+      size_t expect_base = 0;
+      out += std::string(k ? ", " : "") + "[";
+      bool first_pass = true;
+      while (open_rounds_next_pass(cn.data(), cn.size(), plans[k].cap, plans[k].dense_min, cur, p)) {
+        CHECK(p.base == expect_base && p.cnt >= 1 && p.cnt <= plans[k].cap && p.sig_of.size() == p.cnt);
+        CHECK(p.sig_j.size() <= p.cnt && open_rounds_layout(plans[k].cap).total <= kOpenRoundsFwBytesPerItem * plans[k].cap);
+        expect_base += p.cnt;
+        for (size_t i = 0; i < p.cnt; i++) CHECK(p.sig_of[i] < p.sig_j.size() && p.sig_j[p.sig_of[i]] == owner[p.base + i]);
+        out += std::string(first_pass ? "" : ", ") + "[" + std::to_string(p.base) + ", " + std::to_string(p.cnt) + ", " +
+               list_of(p.sig_j) + ", [";
+        first_pass = false;
+        for (size_t t = 0; t < p.tiles.size(); t++) {
+          const TlockTile& tl = p.tiles[t];
+          CHECK(tl.len >= 1 && tl.len <= kTlockTileItems && (size_t)tl.first + tl.len <= p.cnt);
+          for (uint32_t i = tl.first; i < tl.first + tl.len && i < p.cnt; i++) {
+            covered[p.base + i]++;
+            CHECK(tl.sig == kTlockTileMixed || p.sig_of[i] == tl.sig);
+          }
+          out += std::string(t ? ", " : "") + "[" + std::to_string(tl.first) + ", " + std::to_string(tl.len) + ", " +
+                 (tl.sig == kTlockTileMixed ? std::string("-1") : std::to_string(tl.sig)) + "]";
+        }
+        out += "]]";
+      }
+      CHECK(expect_base == n);
+      for (size_t i = 0; i < n; i++) CHECK(covered[i] == 1);  // every item exactly once
+      out += "]";
+    }
+  }
   out += "]}}}";
   puts(out.c_str());
   return 0;

@@ -19,6 +19,8 @@
 #include "../drand_amd/csrc/testops.h"
 #include "../drand_amd/csrc/rlc.h"
 #include "../drand_amd/csrc/tlock.h"
+#include "../drand_amd/csrc/tlockr.h"
+#include "../drand_amd/csrc/hostlogic.h"
 #include "../drand_amd/csrc/tseal.h"
 #include "../drand_amd/csrc/tsealr.h"
 
@@ -910,6 +912,141 @@ static int cmd_tsealr(const char* pkhex) {
   return table_match && two_pair_match ? 0 : 1;
 }
 
+// tlockr <cap> <dense_min> (<sig96hex> <count>)...: the timelock opening across many rounds
+// (drand_amd/csrc/tlockr.h) as the device runs it -- the host's plan of every pass of at most cap items
+// (hostlogic.h open_rounds_next_pass), per pass the signatures it touches decoded and prepared into one
+// word-major table, then every tile's items through tlockr_f in the tile's form: a uniform tile reads a
+// copy of its signature's column (the device's LDS copy), a mixed tile's items read the table itself. Every
+// item also runs the other form ("forms_match"). The U values come on stdin, one 48-byte compressed G1
+// point in hex per line, in packed order. Prints sig_class per signature, class and e (null where the item
+// did not open) per item and the tiles of every pass as [first, len, sig] (sig -1 = mixed).
+static int cmd_tlockr(int argc, char** argv) {
+  using namespace blsv_detail;
+  if (argc < 2 || (argc - 2) % 2) return 2;
+  const size_t cap = strtoull(argv[0], nullptr, 10), dense_min = strtoull(argv[1], nullptr, 10);
+  const size_t m = (size_t)(argc - 2) / 2;
+  if (!cap) return 2;
+  std::vector<std::vector<uint8_t>> sigs;
+  std::vector<uint64_t> counts;
+  for (size_t j = 0; j < m; j++) {
+    sigs.push_back(unhex(argv[2 + 2 * j]));
+    if (sigs.back().size() != 96) return 2;
+    counts.push_back(strtoull(argv[3 + 2 * j], nullptr, 10));
+  }
+  std::vector<std::vector<uint8_t>> us;
+  static char line_buf[256];
+  while (fgets(line_buf, sizeof line_buf, stdin)) {
+    char* save = nullptr;
+    const char* uh = strtok_r(line_buf, " \n", &save);
+    if (!uh) continue;
+    us.push_back(unhex(uh));
+    if (us.back().size() != 48) return 2;
+  }
+  const size_t n = us.size();
+  if (!open_rounds_fits(counts.data(), m, n)) {
+    printf("{\"einval\": true}\n");
+    return 1;
+  }
+  std::vector<int> sig_class(m), classes(n, 0);
+  for (size_t j = 0; j < m; j++) {
+    g2a Q;
+    bool qinf;
+    sig_class[j] = g2_decompress(sigs[j].data(), Q, qinf, true);
+  }
+  std::vector<std::string> enc(n);
+  bool forms_match = true;
+  std::string tiles_json;
+  TlockRoundsCursor cur;
+  TlockRoundsPass p;
+  while (open_rounds_next_pass(counts.data(), m, cap, dense_min, cur, p)) {
+    const size_t M = p.sig_j.size();
+    std::vector<g2a> Q(M);
+    std::vector<uint8_t> qinf(M), qcls(M);
+    std::vector<uint32_t> tab((size_t)TLOCK_TAB_WORDS * M, 0xdeadbeefu);
+    for (size_t j = 0; j < M; j++) {
+      bool inf;
+      qcls[j] = g2_decompress(sigs[p.sig_j[j]].data(), Q[j], inf, true);
+      qinf[j] = inf;
+      if (qcls[j] == REJ_OK && !inf) tlockr_prepare(Q[j], [&](int w, uint32_t v) { tab[tlockr_tab_at(w, M, j)] = v; });
+    }
+    tiles_json += std::string(tiles_json.empty() ? "" : ", ") + "[";
+    for (size_t t = 0; t < p.tiles.size(); t++) {
+      const TlockTile& tl = p.tiles[t];
+      const bool mixed = tl.sig == kTlockTileMixed;
+      tiles_json += std::string(t ? ", " : "") + "[" + std::to_string(tl.first) + ", " + std::to_string(tl.len) + ", " +
+                    (mixed ? std::string("-1") : std::to_string(tl.sig)) + "]";
+      std::vector<uint32_t> col(TLOCK_TAB_WORDS);  // a uniform tile's copy of its column
+      if (!mixed)
+        for (int w = 0; w < TLOCK_TAB_WORDS; w++) col[w] = tab[tlockr_tab_at(w, M, tl.sig)];
+      for (uint32_t lane = 0; lane < tl.len; lane++) {
+        const size_t i = tl.first + lane, gi = p.base + i;
+        const size_t j = mixed ? p.sig_of[i] : tl.sig;
+        g1a U;
+        bool uinf;
+        classes[gi] = g1_decompress(us[gi].data(), U, uinf);
+        if (classes[gi] != REJ_OK) continue;
+        if (qcls[j] != REJ_OK) {
+          classes[gi] = REJ_TLOCK_SIG;
+          continue;
+        }
+        fp12 f = fp12_one();
+        if (!uinf && !qinf[j]) {
+          fp2 parked[3];
+          auto from_table = [&](int step, int c) {
+            const size_t o = tlockr_tab_at(tlockr_coef_word(step, c), M, j);
+            fp2 v;
+            for (int k = 0; k < 12; k++) {
+              v.c0.l[k] = tab[o + (size_t)k * M];
+              v.c1.l[k] = tab[o + (size_t)(12 + k) * M];
+            }
+            return v;
+          };
+          std::vector<uint32_t> own;  // the other form of a mixed tile's item: a copy of its own column
+          if (mixed) {
+            own.resize(TLOCK_TAB_WORDS);
+            for (int w = 0; w < TLOCK_TAB_WORDS; w++) own[w] = tab[tlockr_tab_at(w, M, j)];
+          }
+          const std::vector<uint32_t>& column = mixed ? own : col;
+          auto from_column = [&](int step, int c) {
+            const int o = tlockr_coef_word(step, c);
+            fp2 v;
+            for (int k = 0; k < 12; k++) {
+              v.c0.l[k] = column[o + k];
+              v.c1.l[k] = column[o + 12 + k];
+            }
+            return v;
+          };
+          auto ucoord = [&](int c) { return c == 0 ? U.x : U.y; };
+          auto park = [&](int c, const fp2& v) { parked[c] = v; };
+          auto get = [&](int c) { return parked[c]; };
+          auto sqr = [](const fp12& a) { return fp12_sqr(a); };
+          const fp12 fm = tlockr_f(from_table, ucoord, park, get, sqr);
+          const fp12 fu = tlockr_f(from_column, ucoord, park, get, sqr);
+          forms_match &= fp12_eq(fm, fu);
+          f = mixed ? fm : fu;
+        }
+        uint8_t out[TLOCK_GT_LEN];
+        tlock_encode(out, final_exponentiation(f));
+        enc[gi] = hex_of(out, TLOCK_GT_LEN);
+      }
+    }
+    tiles_json += "]";
+  }
+  printf("{\"sig_class\": [");
+  for (size_t j = 0; j < m; j++) printf("%s%d", j ? ", " : "", sig_class[j]);
+  printf("], \"forms_match\": %s, \"class\": [", forms_match ? "true" : "false");
+  for (size_t i = 0; i < n; i++) printf("%s%d", i ? ", " : "", classes[i]);
+  printf("], \"e\": [");
+  for (size_t i = 0; i < n; i++) {
+    if (enc[i].empty())
+      printf("%snull", i ? ", " : "");
+    else
+      printf("%s\"%s\"", i ? ", " : "", enc[i].c_str());
+  }
+  printf("], \"tiles\": [%s]}\n", tiles_json.c_str());
+  return forms_match ? 0 : 1;
+}
+
 // The batch path's subgroup check of a decoded sigma (not infinity): the call-free line steps of
 // k_miller_lines over |x|'s bits (the lines themselves dropped; they do not depend on the check) and
 // pairing.h miller_t_in_subgroup on the T they leave. close_muls: the Fp products of that closing test.
@@ -958,6 +1095,7 @@ int main(int argc, char** argv) {
   if (argc == 3 && !strcmp(argv[1], "tlock")) return cmd_tlock(argv[2]);
   if (argc == 4 && !strcmp(argv[1], "tseal")) return cmd_tseal(argv[2], strtoull(argv[3], nullptr, 10));
   if (argc == 3 && !strcmp(argv[1], "tsealr")) return cmd_tsealr(argv[2]);
+  if (argc >= 4 && !strcmp(argv[1], "tlockr")) return cmd_tlockr(argc - 2, argv + 2);
   if (argc == 4 && !strcmp(argv[1], "rlc")) return cmd_rlc(argv[2], strtoul(argv[3], nullptr, 10));
   if (argc >= 2 && !strcmp(argv[1], "ops")) return cmd_ops(argc == 3 && !strcmp(argv[2], "list"));
   if (argc == 3 && !strcmp(argv[1], "hash")) return cmd_hash(argv[2]);
@@ -971,8 +1109,9 @@ int main(int argc, char** argv) {
             "       %s tlock sig96hex   (one compressed U in hex per line on stdin)\n"
             "       %s subgroup   (one compressed G2 point in hex per line on stdin)\n"
             "       %s tseal pk48hex round   (one 32-byte scalar in hex per line on stdin)\n"
-            "       %s tsealr pk48hex   (one \"round scalarhex\" per line on stdin)\n",
-            argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
+            "       %s tsealr pk48hex   (one \"round scalarhex\" per line on stdin)\n"
+            "       %s tlockr cap dense_min (sig96hex count)...   (one compressed U in hex per line on stdin)\n",
+            argv[0], argv[0], argv[0], argv[0], argv[0], argv[0], argv[0]);
     return 2;
   }
   auto pk = unhex(argv[1]);
