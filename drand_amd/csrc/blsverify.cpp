@@ -39,6 +39,7 @@ int ensure_workspace(blsv_ctx* c, size_t cnt) {
     // out of HBM (other contexts or ranks on this GPU): halve the pass size and retry
     c->chunk = std::max(kMinChunk, ((want / 2) + 63) & ~size_t(63));
     c->lat_max = std::min(c->lat_max, c->chunk);
+    c->tlock_lat.lat_max = std::min(c->tlock_lat.lat_max, c->chunk);
     c->oom_halvings++;
   }
 }
@@ -116,6 +117,7 @@ int blsv_create(int device, blsv_ctx** out) {
   *out = nullptr;
   blsv_ctx* c = new blsv_ctx();
   c->device = device;
+  c->tlock_lat.lat_max = std::min(tlock_lat_max_env(), c->chunk);
   hipError_t e = hipSetDevice(device);
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking);
@@ -209,6 +211,21 @@ size_t blsv_set_lat_max(blsv_ctx* c, size_t lat_max) {
   return prev;
 }
 
+// cutover of the timelock opening's latency path (include/blsverify.h "timelock"; 0 = off)
+size_t blsv_set_tlock_lat_max(blsv_ctx* c, size_t items) {
+  if (!c) return 0;
+  const size_t prev = c->tlock_lat.lat_max;
+  c->tlock_lat.lat_max = std::min(items, c->chunk);
+  return prev;
+}
+
+int blsv_tlock_lat_stats(blsv_ctx* c, uint64_t* launches, uint64_t* items) {
+  if (!c) return BLSV_EINVAL;
+  if (launches) *launches = c->tlock_lat.launches;
+  if (items) *items = c->tlock_lat.items;
+  return BLSV_OK;
+}
+
 // per-context pass size (include/blsverify.h memory contract)
 size_t blsv_set_chunk(blsv_ctx* c, size_t items) {
   if (!c) return 0;
@@ -223,6 +240,7 @@ size_t blsv_set_chunk(blsv_ctx* c, size_t items) {
   }
   c->chunk = v;
   c->lat_max = std::min(c->lat_max, v);
+  c->tlock_lat.lat_max = std::min(c->tlock_lat.lat_max, v);
   return prev;
 }
 

@@ -258,6 +258,24 @@ inline size_t lat_max_env() {
   return v;
 }
 
+// Cutover of the timelock opening's latency path (blsv_set_tlock_lat_max): BLSV_TLOCK_LAT_MAX, parsed as
+// BLSV_LAT_MAX is, else 0 = off.
+inline size_t tlock_lat_max_env() {
+  static const size_t v = [] {
+    const char* e = getenv("BLSV_TLOCK_LAT_MAX");
+    if (!e) return size_t(0);
+    char* end = nullptr;
+    errno = 0;
+    const unsigned long long x = strtoull(e, &end, 10);
+    if (end == e || *end != '\0' || errno == ERANGE || e[0] == '-') {
+      fprintf(stderr, "blsverify: ignoring BLSV_TLOCK_LAT_MAX=\"%s\" (not a non-negative integer); it stays 0\n", e);
+      return size_t(0);
+    }
+    return (size_t)std::min<unsigned long long>(x, kMaxChunk);
+  }();
+  return v;
+}
+
 struct rlc_state {
   size_t group = kRlcGroupDefault;
   bool seed_pinned = false;  // blsv_test_rlc_seed
@@ -305,6 +323,18 @@ struct tlockr_state {
   size_t dense_min = kTlockDenseMinDefault;
   uint64_t items = 0;  // blsv_tlock_open_rounds_stats
   DBuf prepared;
+};
+
+// Timelock opening on the latency path (blsv_set_tlock_lat_max, k_lat_tlock.hip): host calls of up to
+// lat_max items, one workgroup per item. It shares nothing with the batch paths: its own device buffer
+// (hostlogic.h tlock_lat_layout) and host staging of a call's results, its own counters; the sigma cache
+// of tlock_state, the pipeline staging and every other counter stay as they are.
+struct tlock_lat_state {
+  size_t lat_max = 0;                // never above the chunk
+  uint64_t launches = 0, items = 0;  // blsv_tlock_lat_stats
+  DBuf buf;
+  std::vector<uint8_t> up, down;
+  TlockLatPlan plan;
 };
 
 struct blsv_ctx {
@@ -372,6 +402,7 @@ struct blsv_ctx {
   tseal_state tseal;
   tsealr_state tsealr;
   tlockr_state tlockr;
+  tlock_lat_state tlock_lat;
 };
 
 #define HIPCHK(ctx, expr)                                                             \

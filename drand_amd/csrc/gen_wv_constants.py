@@ -154,6 +154,11 @@ def main():
     for i in range(16):
         add(f"PC{i}", [pl[(l % 32) - i] if i <= (l % 32) <= i + 15 else 0 for l in range(64)])
     add_dup("C1200_DUP", pow(2, 1200, P), montgomery=False)  # wave GCD's y^-1 (y = a 2^400) -> 400-form
+    # G1's endomorphism (x, y) -> (beta x, y), beta the cube root of unity 2^((p-1)/3): it acts on G1 as
+    # [-x^2] (whash.h g1_in_subgroup; the other root beta^2 acts as [x^2 - 1] and would reject all of G1)
+    beta = pow(2, (P - 1) // 3, P)
+    assert beta != 1 and pow(beta, 3, P) == 1
+    add_dup("G1_BETA", beta)
     np25 = limbs25((-pow(P, -1, R)) % R)
     p_over_r = P / R
 

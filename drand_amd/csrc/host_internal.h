@@ -157,6 +157,16 @@ int decode_g1(blsv_ctx* c, const uint8_t* pk48, size_t cnt, DBuf& tab, DBuf& inf
 // n messages packed back to back (msg_lens[i] bytes each) into in_msgs / in_off / in_len
 int upload_messages(blsv_ctx* c, const uint8_t* msgs, const uint32_t* msg_lens, size_t n);
 
+// ---- tlock.cpp: a host call of n >= 1 items on the latency path (hostlogic.h tlock_lat_routes). The m
+// signatures, item i under sig_of[i] (null: all under signature 0), the n_idle signatures idle[] classed
+// alone. o points into the context's host staging, valid until the next call; copy_out hands the items over.
+struct TlockLatOut {
+  const uint8_t *gt, *cls, *sig_cls;  // n x 576 bytes, n item classes, m signature classes
+};
+int tlock_lat_run(blsv_ctx* c, const uint8_t* sigs96, size_t m, const uint32_t* sig_of, const uint32_t* idle,
+                  size_t n_idle, const uint8_t* us48, size_t n, TlockLatOut& o);
+void tlock_lat_copy_out(const TlockLatOut& o, size_t n, uint8_t* out_gt576, uint8_t* ok, uint8_t* reject_class);
+
 // ---- tseal.cpp: the key a sealing call runs under -- pk48, or the group key (BLSV_ENOGROUP without one)
 int seal_key(blsv_ctx* c, const uint8_t* pk48, const uint8_t** key);
 

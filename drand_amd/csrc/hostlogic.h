@@ -403,5 +403,52 @@ inline OpenRoundsLayout open_rounds_layout(size_t cap) {
 }
 constexpr size_t kOpenRoundsFwBytesPerItem = 2 + 4 + 4 + sizeof(TlockTile);
 
+// ---------------------------------------------------------------- timelock opening on the latency path
+// blsv_set_tlock_lat_max: a host call of 1 .. lat_max items goes to k_lat_tlock, one workgroup per item.
+// A call across rounds also gives every signature without items a workgroup of its own, so it takes the
+// latency path only while those are no more than lat_max either (n_idle: tlock_lat_plan's count).
+inline bool tlock_lat_routes(size_t n, size_t n_idle, size_t lat_max) {
+  return n >= 1 && n <= lat_max && n_idle <= lat_max;
+}
+// The plan of a call across rounds (counts as open_rounds_fits accepted them): sig_of[i] = the signature
+// of item i, idle = the signatures without items, ascending. With max_idle, stops and returns false once
+// more than max_idle signatures are idle (the call is not for the latency path; the plan is then partial).
+struct TlockLatPlan {
+  std::vector<uint32_t> sig_of, idle;
+};
+inline bool tlock_lat_plan(const uint64_t* counts, size_t m, size_t max_idle, TlockLatPlan& p) {
+  p.sig_of.clear();
+  p.idle.clear();
+  for (size_t j = 0; j < m; j++) {
+    if (counts[j]) {
+      p.sig_of.insert(p.sig_of.end(), (size_t)counts[j], (uint32_t)j);
+    } else {
+      if (p.idle.size() == max_idle) return false;
+      p.idle.push_back((uint32_t)j);
+    }
+  }
+  return true;
+}
+// One device buffer per call: what the host uploads in one copy (the m signatures, the n compressed U, and
+// for a call across rounds sig_of and idle), then, 64-byte aligned, what one download brings back (the n x
+// 576 bytes, the n item classes, the m signature classes). Every offset of a word array is 4-byte aligned.
+struct TlockLatLayout {
+  size_t o_sigs, o_us, o_sigof, o_idle, in_total, o_gt, o_cls, o_sigcls, out_total, total;
+};
+inline TlockLatLayout tlock_lat_layout(size_t m, size_t n, bool rounds, size_t n_idle) {
+  TlockLatLayout l;
+  l.o_sigs = 0;
+  l.o_us = 96 * m;
+  l.o_sigof = l.o_us + BLSV_U_LEN * n;
+  l.o_idle = l.o_sigof + (rounds ? 4 * n : 0);
+  l.in_total = l.o_idle + 4 * n_idle;
+  l.o_gt = (l.in_total + 63) & ~size_t(63);
+  l.o_cls = l.o_gt + BLSV_GT_LEN * n;
+  l.o_sigcls = l.o_cls + n;
+  l.out_total = BLSV_GT_LEN * n + n + m;
+  l.total = l.o_gt + l.out_total;
+  return l;
+}
+
 }  // namespace blsv_detail
 #pragma GCC visibility pop

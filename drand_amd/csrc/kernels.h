@@ -182,6 +182,13 @@ void launch_lat_unchained(const uint64_t* rounds, uint64_t first_round, const ui
 void launch_lat_messages(const uint8_t* msgs, const uint64_t* off, const uint32_t* len, const uint8_t* sigs,
                          size_t stride, size_t offset, size_t cnt, const uint32_t* pk_tab, const uint8_t* pk_inf,
                          const uint32_t* pk_idx, uint8_t* cls, uint32_t* S, uint8_t* s_inf, hipStream_t st);
+// timelock opening on the latency path (k_lat_tlock.hip): one workgroup per item, E_i = e(U_i, sigma_j)^3
+// with j = sig_of[i] (0 when sig_of is null) -> out (n_items x 576 bytes, 4-byte aligned, zeros for a
+// rejected item), cls[i] (the item's class: U's own, else BLSV_REJ_TLOCK_SIG under a rejected signature)
+// and sig_cls[j]; n_idle further workgroups class the signatures idle[k], which have no item
+void launch_lat_tlock(const uint8_t* sigs, const uint32_t* sig_of, const uint8_t* us, size_t n_items,
+                      const uint32_t* idle, size_t n_idle, uint8_t* out, uint8_t* cls, uint8_t* sig_cls,
+                      hipStream_t st);
 
 // ---- group / threshold / signing kernels (k_misc.hip)
 // decompress cnt G1 points (48 B each) -> pk table entries + inf flags + reject class

@@ -3,6 +3,8 @@
 // exponentiation with its capture output and the Gt encoding, all in the pipeline staging
 // (engine_ctx.h lists which buffer holds what). It shares the staging with the verification passes
 // (verify.cpp) but none of their stages, so it keeps a pass loop of its own.
+// Also the latency path of the host forms (blsv_set_tlock_lat_max; tlock_lat_run, used by tlockr.cpp too):
+// one workgroup per item in one launch (k_lat_tlock.hip), outside the staging, the cache and the counters.
 #include "host_internal.h"
 
 // Decodes and prepares sigma on st unless it is the cached one; its class is read back (the one
@@ -92,6 +94,41 @@ static int tlock_passes(blsv_ctx* c, bool host, const uint8_t* us, size_t n, uin
   return BLSV_OK;
 }
 
+// The latency path (blsv_set_tlock_lat_max, k_lat_tlock.hip): one upload of the call's inputs, one launch
+// with a workgroup per item and per idle signature, one download of everything it wrote. The results stay
+// in the context's host staging (o points into it) for the caller to copy out: blsv_tlock_open hands
+// nothing over under a rejected sigma. sig_of == nullptr: every item under signature 0.
+int tlock_lat_run(blsv_ctx* c, const uint8_t* sigs96, size_t m, const uint32_t* sig_of, const uint32_t* idle,
+                  size_t n_idle, const uint8_t* us48, size_t n, TlockLatOut& o) {
+  tlock_lat_state& t = c->tlock_lat;
+  const TlockLatLayout l = tlock_lat_layout(m, n, sig_of != nullptr, n_idle);
+  HIPCHK(c, t.buf.ensure(l.total));
+  t.up.resize(l.in_total);
+  memcpy(t.up.data() + l.o_sigs, sigs96, 96 * m);
+  memcpy(t.up.data() + l.o_us, us48, BLSV_U_LEN * n);
+  if (sig_of) memcpy(t.up.data() + l.o_sigof, sig_of, 4 * n);
+  if (n_idle) memcpy(t.up.data() + l.o_idle, idle, 4 * n_idle);
+  uint8_t* d = t.buf.as<uint8_t>();
+  HIPCHK(c, h2d(c, d, t.up.data(), l.in_total));
+  blsk::launch_lat_tlock(d + l.o_sigs, sig_of ? (const uint32_t*)(d + l.o_sigof) : nullptr, d + l.o_us, n,
+                         (const uint32_t*)(d + l.o_idle), n_idle, d + l.o_gt, d + l.o_cls, d + l.o_sigcls, c->stream);
+  HIPCHK(c, hipGetLastError());
+  t.down.resize(l.out_total);
+  HIPCHK(c, download_sync(c, {{t.down.data(), d + l.o_gt, l.out_total}}));
+  o.gt = t.down.data();
+  o.cls = o.gt + BLSV_GT_LEN * n;
+  o.sig_cls = o.cls + n;
+  t.launches++;
+  t.items += n;
+  return BLSV_OK;
+}
+
+void tlock_lat_copy_out(const TlockLatOut& o, size_t n, uint8_t* out_gt576, uint8_t* ok, uint8_t* reject_class) {
+  memcpy(out_gt576, o.gt, BLSV_GT_LEN * n);
+  if (reject_class) memcpy(reject_class, o.cls, n);
+  for (size_t i = 0; i < n; i++) ok[i] = o.cls[i] == BLSV_REJ_OK;
+}
+
 extern "C" {
 
 int blsv_tlock_open(blsv_ctx* c, const uint8_t* sig96, const uint8_t* us48, size_t n, uint8_t* out_gt576, uint8_t* ok,
@@ -99,6 +136,16 @@ int blsv_tlock_open(blsv_ctx* c, const uint8_t* sig96, const uint8_t* us48, size
   if (!c) return BLSV_EINVAL;
   if (!sig96 || (n && (!us48 || !out_gt576 || !ok))) return fail(c, BLSV_EINVAL, "tlock_open: bad arguments");
   (void)hipSetDevice(c->device);
+  if (tlock_lat_routes(n, 0, std::min(c->tlock_lat.lat_max, c->chunk))) {
+    TlockLatOut o;
+    const int rl = tlock_lat_run(c, sig96, 1, nullptr, nullptr, 0, us48, n, o);
+    if (rl) return rl;
+    if (sig_class) *sig_class = o.sig_cls[0];
+    if (o.sig_cls[0] != BLSV_REJ_OK)
+      return fail(c, BLSV_EINVAL, "tlock_open: signature rejected (class %d)", (int)o.sig_cls[0]);
+    tlock_lat_copy_out(o, n, out_gt576, ok, reject_class);
+    return BLSV_OK;
+  }
   int rc = tlock_prepare_sig(c, sig96, c->stream, sig_class);
   if (rc) return rc;
   if (!n) return BLSV_OK;

@@ -159,6 +159,16 @@ int blsv_tlock_open_rounds(blsv_ctx* c, const uint8_t* sigs96, const uint64_t* c
   if ((m && (!sigs96 || !counts)) || (n && (!us48 || !out_gt576 || !ok)) || !open_rounds_fits(counts, m, n))
     return fail(c, BLSV_EINVAL, "tlock_open_rounds: bad arguments");
   (void)hipSetDevice(c->device);
+  const size_t lat_max = std::min(c->tlock_lat.lat_max, c->chunk);
+  if (tlock_lat_routes(n, 0, lat_max) && tlock_lat_plan(counts, m, lat_max, c->tlock_lat.plan)) {
+    const TlockLatPlan& p = c->tlock_lat.plan;
+    TlockLatOut o;
+    const int rl = tlock_lat_run(c, sigs96, m, p.sig_of.data(), p.idle.data(), p.idle.size(), us48, n, o);
+    if (rl) return rl;
+    if (sig_class) memcpy(sig_class, o.sig_cls, m);
+    tlock_lat_copy_out(o, n, out_gt576, ok, reject_class);
+    return BLSV_OK;
+  }
   uint8_t* d_sc = nullptr;
   if (sig_class && m) {
     HIPCHK(c, c->misc.ensure(m));

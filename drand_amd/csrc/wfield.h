@@ -45,7 +45,7 @@ namespace wv {
 // flag on (blsv_lat_trace_enable), wave-lane 0 of item 0 (block 0) stamps the device wall clock at the
 // marks of wvteam.h verify_team; a no-op in every other block, in production launches and on the host.
 constexpr int LAT_TRACE_N = 16;
-#ifdef WV_HOST
+#if defined(WV_HOST) || defined(WV_NO_TRACE)  // WV_NO_TRACE: a translation unit without the trace's globals
 #define WV_MARK(k) ((void)0)
 #else
 extern __device__ uint64_t g_lat_trace[LAT_TRACE_N];

@@ -318,4 +318,69 @@ WVI uint8_t g2_decompress(const uint8_t* in, F& ox, F& oy, bool& is_inf, bool su
   return bls::REJ_OK;
 }
 
+// ------------------------------------------------------------------ G1 decompression
+// A G1 point rides in the G2 types with every coordinate's imaginary half zero ([a | 0]): the Jacobian
+// formulas of wcurve.h never touch the curve constant, so g2_dbl / g2_add / g2_mul_x_abs and their team
+// forms compute on y^2 = x^3 + 4 as they stand, and the imaginary halves stay zero.
+//
+// P in G1 <=> sigma(P) == [-x^2] P for sigma(x, y) = (beta x, y) (Scott, "A note on group membership tests
+// for G1, G2 and GT on BLS pairing-friendly curves", 2021): -x^2 is sigma's eigenvalue on G1, and no other
+// point of E(Fp) satisfies it. Two [|x|] chains against the four of curve.h g1_in_subgroup's
+// [x^2]([x^2] P - P) == -P; on curve points the two tests give the same verdict. Compared as
+// [x^2] P == -sigma(P) = (beta X, -Y, Z).
+WVI G2J g1_neg_sigma(const G2J& p) { return {mulp(p.x, cst(WC_G1_BETA)), neg<0>(p.y), p.z}; }
+WVI bool g1_in_subgroup(const G2J& p) {
+  if (g2_is_inf(p)) return true;
+  return g2_eq(g2_mul_x_abs(g2_mul_x_abs(p)), g1_neg_sigma(p));
+}
+
+// 48-byte compressed point (wave-uniform bytes) -> affine (x, y) in the embedded form, curve.h
+// g1_decompress's rules and check order: flag, infinity form, x < p, y^2 = x^3 + 4 (the root as
+// rhs^((p+1)/4) = rhs rhs^((p-3)/4), pw computing the power), sign (y > (p-1)/2), subgroup; with
+// subgroup = false that last check is left to the caller (wvteam.h runs it on a team)
+template <class Pow = PowSelf>
+WVI uint8_t g1_decompress(const uint8_t* in, F& ox, F& oy, bool& is_inf, Pow pw = Pow(), bool subgroup = true) {
+  is_inf = false;
+  const uint8_t b0 = in[0];
+  if (!(b0 & 0x80)) return bls::REJ_FLAG;
+  if (b0 & 0x40) {
+    uint32_t acc = (b0 != 0xc0);
+    for (int i = 1; i < 48; i++) acc |= in[i];
+    if (acc) return bls::REJ_INF_NONZERO;
+    is_inf = true;
+    return bls::REJ_OK;
+  }
+  const bool sign = (b0 & 0x20) != 0;
+  // x = bytes 0..47 (flags masked), big-endian: lane k of half 0 takes bits 25k .. 25k+24
+  const V l = lane_id(), k = l & 15u;
+  uint32_t wd[13];  // little-endian 32-bit words of the 384-bit field, + 1 zero word
+  for (int i = 0; i < 12; i++) {
+    const uint8_t* q = in + 44 - 4 * i;
+    wd[i] = ((uint32_t)q[0] << 24) | ((uint32_t)q[1] << 16) | ((uint32_t)q[2] << 8) | (uint32_t)q[3];
+  }
+  wd[11] &= 0x1fffffffu;
+  wd[12] = 0;
+  V v = vsplat(0);
+  for (int kk = 0; kk < 16; kk++) {
+    const int bit = 25 * kk, wi = bit >> 5, sh = bit & 31;
+    const uint32_t lo = wd[wi], hi = wi + 1 < 13 ? wd[wi + 1] : 0u;
+    const uint32_t val = (uint32_t)((((uint64_t)hi << 32) | lo) >> sh) & M25;
+    v = sel(k == (uint32_t)kk, vsplat(val), v);
+  }
+  const V limbs = sel(l < 16u, v, vsplat(0));
+  if (ge_halves(limbs, cword(WC_P_DUP)) & 1u) return bls::REJ_X_GE_P;
+  const F x = mulp(mkF(limbs, 1.0), cst(WC_R2_DUP));                 // [x | 0]
+  const F rhs = dot(sqr2(x), x, cst(WC_POS4), cst(WC_ONE2));         // x^3 + 4
+  const F a = dup0(rhs);
+  const F s = mulp(pw(a), a);
+  if (zero_halves(sub<0>(sqrp(s), a)) != 3u) return bls::REJ_NOT_ON_CURVE;
+  F y = lo_only(s);
+  const bool largest = (ge_halves(raw_canon(y), cword(WC_PP1H_DUP)) & 1u) != 0;
+  if (largest != sign) y = mul2(y, cst(WC_NEG1));  // -y, reduced (a later subtrahend)
+  if (subgroup && !g1_in_subgroup({x, y, cst(WC_ONE2)})) return bls::REJ_NOT_IN_SUBGROUP;
+  ox = x;
+  oy = y;
+  return bls::REJ_OK;
+}
+
 }  // namespace wv

@@ -123,8 +123,8 @@ WVI W12 w12_pow_x_abs(const W12& g) {
   return r;
 }
 
-// f0: the Miller product before its final conjugation, f = conj(f0)
-WVI bool final_exp_is_one(const W12& f0) {
+// f^(3 (p^12 - 1) / r) for f0: the Miller product before its final conjugation, f = conj(f0)
+WVI W12 final_exp(const W12& f0) {
   // easy part: g = f^((p^6 - 1)(p^2 + 1)); f^(p^6 - 1) = conj(f) f^-1 = f0 conj(f0^-1)
   const W12 t = w12_mul(f0, w12_inv<true>(f0));
   const W12 g = w12_mul(w12_frob2(t), t);
@@ -137,8 +137,41 @@ WVI bool final_exp_is_one(const W12& f0) {
   e = w12_mul(e, w12_frob2(c));
   e = w12_mul(e, w12_conj(c));
   e = w12_mul(e, w12_cyc_sqr(g));
-  e = w12_mul(e, g);
-  return w12_is_one(e);
+  return w12_mul(e, g);
+}
+WVI bool final_exp_is_one(const W12& f0) { return w12_is_one(final_exp(f0)); }
+
+// ------------------------------------------------------------------ Gt encoding
+// One w-power coefficient of an Fp12 value into its 96 bytes of the 576-byte encoding (include/blsverify.h
+// "timelock": twelve canonical Fp values out of Montgomery form, 48 bytes big-endian each, highest tower
+// coefficient first -- the w-powers 5, 3, 1, 4, 2, 0, each as imaginary then real part). out: the item's
+// 144 words. Lane j < 24 assembles word j of the 96 bytes from the strict limbs, which pass through this
+// wave's LDS scratch (the product area's negation words, restaged by the next product), and stores it.
+WVI int gt_pos(int k) { return (k & 1) ? (5 - k) / 2 : 3 + (4 - k) / 2; }
+WVI void gt_store_words(uint32_t* out, int k, const V& words) {
+  const V l = lane_id();
+  gst_if(l < 24u, out, (uint32_t)(24 * gt_pos(k)) + l, words);
+}
+WVI void gt_encode_c(uint32_t* out, int k, const F& c) {
+  uint32_t* lds = wave_lds() + L_BZ;
+  const V l = lane_id();
+  const V r = raw_canon(c);
+  wsync();
+  lds_st(lds, l, r);
+  wsync();
+  // word j: half 1 (imaginary) first, most significant word first; little-endian word wi = bits 32 wi ..
+  const V j = sel(l < 24u, l, vsplat(0));
+  const V h = sel(j < 12u, vsplat(1), vsplat(0)), wi = 11u - (j - sel(j < 12u, vsplat(0), vsplat(12)));
+  const V bit = wi * 32u, k0 = (bit * 1311u) >> 15, s = bit - k0 * 25u;  // k0 = bit / 25 <= 14 (bit <= 352)
+  const V base = h * 32u;
+  const V a0 = lds_ld(lds, base + k0);
+  const V a1 = lds_ld(lds, base + sel(k0 + 1u < 16u, k0 + 1u, vsplat(16)));  // word 16 / 48: an odd row's zero
+  const V a2 = lds_ld(lds, base + sel(k0 + 2u < 16u, k0 + 2u, vsplat(16)));
+  wsync();
+  // limb k0 from bit s, limb k0 + 1 from bit 25 - s, limb k0 + 2 from bit 50 - s (inside the word when s > 18)
+  const V w = (a0 >> s) | (a1 << (25u - s)) | sel(s > 18u, a2 << ((50u - s) & 31u), vsplat(0));
+  const V be = (w >> 24) | ((w >> 8) & 0xff00u) | ((w << 8) & 0xff0000u) | (w << 24);
+  gt_store_words(out, k, be);
 }
 
 }  // namespace wv

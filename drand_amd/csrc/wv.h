@@ -233,6 +233,10 @@ WVI void lds_st(uint32_t* base, const V& off, const V& x) { WV_LANES base[off.v[
 // global / constant table loads, per-lane index
 WVI V gld(const uint32_t* base, const V& idx) { return lds_ld(base, idx); }
 WVI void gst(uint32_t* base, const V& idx, const V& x) { lds_st(base, idx, x); }
+// the lanes of m store, the others touch nothing
+WVI void gst_if(const M& m, uint32_t* base, const V& idx, const V& x) {
+  WV_LANES if (m.v[l]) base[idx.v[l]] = x.v[l];
+}
 #undef WV_LANES
 }  // namespace wv
 
@@ -297,6 +301,9 @@ WVI V lds_ld(const uint32_t* base, V off) { return base[off]; }
 WVI void lds_st(uint32_t* base, V off, V x) { base[off] = x; }
 WVI V gld(const uint32_t* base, V idx) { return base[idx]; }
 WVI void gst(uint32_t* base, V idx, V x) { base[idx] = x; }
+WVI void gst_if(M m, uint32_t* base, V idx, V x) {
+  if (m) base[idx] = x;
+}
 }  // namespace wv
 #endif
 

@@ -55,4 +55,35 @@ WVI uint8_t verify_item(const uint8_t* sig, const uint32_t (&b0)[8], const uint3
   return final_exp_is_one(f0) ? bls::REJ_OK : bls::REJ_PAIRING;
 }
 
+// BLSV_REJ_TLOCK_SIG (tlockr.h): the class of an item whose own U decodes but whose signature did not
+constexpr uint8_t REJ_TLOCK_SIG = 9;
+// the item's class from its two decodes: U's own class first, as the batch path reports it
+WVI uint8_t tlock_class(uint8_t u_cls, uint8_t sig_cls) {
+  return u_cls != bls::REJ_OK ? u_cls : sig_cls != bls::REJ_OK ? REJ_TLOCK_SIG : bls::REJ_OK;
+}
+
+// One timelock opening (include/blsverify.h "timelock"): E = e(U, sigma)^3 for the 96-byte compressed
+// signature and the 48-byte compressed U, encoded into out (the item's 576 bytes as 144 words; zeros for
+// a rejected item). Returns the item's class and sets sig_cls, the signature's own decode class. A pair
+// with U or sigma at infinity is skipped: E = 1. The specification of wvteam.h tlock_team.
+WVI uint8_t tlock_item(const uint8_t* sig, const uint8_t* u48, uint32_t* out, uint8_t& sig_cls) {
+  F sx, sy, ux, uy;
+  bool s_inf, u_inf;
+  sig_cls = g2_decompress(sig, sx, sy, s_inf);
+  const uint8_t cls = tlock_class(g1_decompress(u48, ux, uy, u_inf), sig_cls);
+  if (cls != bls::REJ_OK) {
+    for (int k = 0; k < 6; k++) gt_store_words(out, k, vsplat(0));
+    return cls;
+  }
+  W12 e = w12_one();
+  if (!u_inf && !s_inf) {
+    MPair pr[2];
+    const bool active[2] = {true, false};
+    pr[0] = mpair(dup0(ux), dup0(uy), sx, sy);
+    e = final_exp(miller_loop(pr, active));
+  }
+  for (int k = 0; k < 6; k++) gt_encode_c(out, k, e.c[k]);
+  return cls;
+}
+
 }  // namespace wv

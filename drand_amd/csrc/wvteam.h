@@ -744,8 +744,8 @@ WVI void team_w12_inv_conj(Team& t, int f) {
   team_sync(t);
 }
 
-// wpairing.h final_exp_is_one of the Miller value in slots f0 (unconjugated)
-WVI bool team_final_exp_is_one(Team& t, int f0) {
+// wpairing.h final_exp of the Miller value in slots f0 (unconjugated): the value lands in W_A
+WVI void team_final_exp(Team& t, int f0) {
   team_w12_inv_conj(t, f0);  // conj(f0^-1)
   team_op(t, W_T, [&](int k) { return w12_mul_c(xld_w12(f0), xld_w12(W_INV), k); });
   team_op(t, W_U, [&](int k) { return w12_frob2_c(xld_w12(W_T), k); });
@@ -769,6 +769,10 @@ WVI bool team_final_exp_is_one(Team& t, int f0) {
   team_op_cyc(t, W_U, [&](int k) { return w12_cyc_sqr_c(xld_w12(W_G), k); });
   team_op(t, W_P, [&](int k) { return w12_mul_c(xld_w12(W_A), xld_w12(W_U), k); });
   team_op(t, W_A, [&](int k) { return w12_mul_c(xld_w12(W_P), xld_w12(W_G), k); });
+}
+// wpairing.h final_exp_is_one
+WVI bool team_final_exp_is_one(Team& t, int f0) {
+  team_final_exp(t, f0);
   // e == 1: coefficient k checked by wave k, the six verdicts through scalar words
   for (int k = t.id; k < 6; k += t.n) {
     const F c = xld(W_A + k);
@@ -877,6 +881,133 @@ WVI uint8_t verify_team(const uint8_t* sig, const uint32_t (&b0)[8], const uint3
   const bool one = team_final_exp_is_one(all, f);
   if (w == 0) WV_MARK(7);
   return one ? bls::REJ_OK : bls::REJ_PAIRING;
+}
+
+// ------------------------------------------------------------------ the timelock item
+// wverify.h tlock_item run by the eight waves of a workgroup (each wave calls it), on verify_team's plan
+// with U's decode and subgroup check in the place of the hash:
+//
+//   phase A  wave 0: decompression of U (whash.h g1_decompress; wave 5 multiplying for its square root
+//            through the hash ring), then its subgroup check by the hash team (waves 0, 4, 5): the two
+//            [|x|] chains of g1_in_subgroup as team_mul_x_abs, in the key pair's area
+//            wave 1: decompression of the signature (wave 2 multiplying), then its subgroup check
+//            waves 2, 3, 6, 7: as soon as both points are there, the Miller loop of the one pair
+//            e(U, sigma) -- the two subgroup checks run beside it, their verdicts join at the end
+//   phase C  all eight: the final exponentiation, then the six coefficients encoded by six waves
+//
+// There is no phase B: one pair, and its loop is the one that overlaps the checks.
+constexpr int CTR_UDEC = 14;  // the decoded U's hand-off
+constexpr int XW_UCLS = 5, XW_UINF = 6, XW_USUB = 7;
+constexpr int S_UX = S_HX, S_UY = S_HY;  // U affine, in the hash's slots
+constexpr int G1_DEC_POWS = 1;           // whash.h g1_decompress (none when it rejects before its root)
+
+// whash.h g1_in_subgroup of the affine point in S_UX, S_UY by the hash team; the first wave's verdict
+WVI bool team_g1_in_subgroup(Team& t) {
+  const G2J p = {xld(S_UX), xld(S_UY), cst(WC_ONE2)};
+  if (t.id == 0) {
+    xst_g2(HS_P, p);
+    xst_g2(HS_ACC, p);
+  }
+  team_sync(t);
+  team_mul_x_abs(t, HS_P, HS_ACC);
+  if (t.id == 0) xst_g2(HS_Q2, xld_g2(HS_ACC));
+  team_sync(t);
+  team_mul_x_abs(t, HS_Q2, HS_ACC);  // [x^2] P
+  return t.id == 0 ? g2_eq(xld_g2(HS_ACC), g1_neg_sigma(p)) : true;
+}
+
+// verify_team's signature branch: wave 1 decodes (class, flag and point through XW_CLS, XW_SINF, S_SX,
+// S_SY, posted on CTR_DEC) and then checks the subgroup (XW_SUB); wave 2 multiplies for its roots
+WVI void team_sig_decode(const uint8_t* sig, int w) {
+  RingCounts rc;
+  if (w == 1) {
+    F x, y;
+    bool inf;
+    const uint8_t c = g2_decompress(sig, x, y, inf, false, PowRing{&SIG_RING, &rc});
+    if (c == bls::REJ_OK && !inf) {
+      xst(S_SX, x);
+      xst(S_SY, y);
+    }
+    xst_word(XW_CLS, c);
+    xst_word(XW_SINF, inf);
+    flag_post(CTR_DEC);
+    const bool sub_ok = c != bls::REJ_OK || inf || g2_in_subgroup({x, y, cst(WC_ONE2)});
+    xst_word(XW_SUB, sub_ok);
+  } else if (w == 2) {
+    for (int k = 0; k < DEC_POWS; k++)
+      if (!ring_pow_consume(SIG_RING, bls::EXP_P_MINUS_3_DIV_4, rc, CTR_DEC)) break;
+  }
+}
+// the signature's class once every wave has passed a whole-team sync behind team_sig_decode
+WVI uint8_t team_sig_class() {
+  const uint8_t c = (uint8_t)xld_word(XW_CLS);
+  return c == bls::REJ_OK && !xld_word(XW_SUB) ? (uint8_t)bls::REJ_NOT_IN_SUBGROUP : c;
+}
+
+// the class of a signature alone (subgroup check included), for the signatures of rounds without items
+WVI uint8_t sig_class_team(const uint8_t* sig) {
+  Team all = make_team(ALL_WAVES, CTR_ALL);
+  team_sig_decode(sig, wave_id());
+  team_sync(all);
+  return team_sig_class();
+}
+
+// every wave returns the same class and sets the same sig_cls; out: the item's 576 bytes as 144 words
+WVI uint8_t tlock_team(const uint8_t* sig, const uint8_t* u48, uint32_t* out, uint8_t& sig_cls) {
+  const int w = wave_id();
+  Team all = make_team(ALL_WAVES, CTR_ALL);
+  if ((HASH_TEAM >> w) & 1u) {
+    Team th = make_team(HASH_TEAM, CTR_HASH);
+    RingCounts rc;
+    if (w == 0) {
+      F x, y;
+      bool inf;
+      const uint8_t c = g1_decompress(u48, x, y, inf, PowRing{&HASH_RING, &rc}, false);
+      if (c == bls::REJ_OK && !inf) {
+        xst(S_UX, x);
+        xst(S_UY, y);
+      }
+      xst_word(XW_UCLS, c);
+      xst_word(XW_UINF, inf);
+      flag_post(CTR_UDEC);
+    } else if (w == 5) {
+      for (int k = 0; k < G1_DEC_POWS; k++)
+        if (!ring_pow_consume(HASH_RING, bls::EXP_P_MINUS_3_DIV_4, rc, CTR_UDEC)) break;
+    }
+    flag_wait(CTR_UDEC, 1);
+    bool sub_ok = true;
+    if (xld_word(XW_UCLS) == bls::REJ_OK && !xld_word(XW_UINF)) sub_ok = team_g1_in_subgroup(th);
+    if (w == 0) xst_word(XW_USUB, sub_ok);
+  } else if (w == 1) {
+    team_sig_decode(sig, w);
+  } else {
+    Team t1 = make_team(SIG_TEAM, CTR_SIG);
+    team_sig_decode(sig, w);
+    flag_wait(CTR_DEC, 1);
+    flag_wait(CTR_UDEC, 1);
+    if (xld_word(XW_CLS) == bls::REJ_OK && !xld_word(XW_SINF) && xld_word(XW_UCLS) == bls::REJ_OK &&
+        !xld_word(XW_UINF)) {
+      const MPair m = mpair(dup0(xld(S_UX)), dup0(xld(S_UY)), xld(S_SX), xld(S_SY));
+      const int f1 = team_miller(t1, m, TB1);
+      if (t1.id == 0) xst_word(XW_F1, (uint32_t)f1);
+    }
+  }
+  team_sync(all);
+  sig_cls = team_sig_class();
+  uint8_t ucls = (uint8_t)xld_word(XW_UCLS);
+  if (ucls == bls::REJ_OK && !xld_word(XW_USUB)) ucls = bls::REJ_NOT_IN_SUBGROUP;
+  const uint8_t cls = tlock_class(ucls, sig_cls);
+  if (cls != bls::REJ_OK) {
+    for (int k = all.id; k < 6; k += all.n) gt_store_words(out, k, vsplat(0));
+    return cls;
+  }
+  if (xld_word(XW_UINF) || xld_word(XW_SINF)) {  // the pair is skipped: E = 1
+    for (int k = all.id; k < 6; k += all.n) gt_encode_c(out, k, k == 0 ? cst(WC_ONE2) : zero());
+    return cls;
+  }
+  team_final_exp(all, (int)xld_word(XW_F1));
+  for (int k = all.id; k < 6; k += all.n) gt_encode_c(out, k, xld(W_A + k));
+  return cls;
 }
 
 

@@ -501,6 +501,18 @@ class Engine:
         tile uniform, 2^64 - 1 = every tile mixed, 0 = the default); returns the previous value."""
         return int(self.lib.blsv_set_tlock_dense_min(self._h, int(items)))
 
+    def set_tlock_lat_max(self, items):
+        """blsv_set_tlock_lat_max: tlock_open / tlock_open_rounds calls of 1 .. items ciphertexts run on the
+        latency path, one workgroup per ciphertext (0 = off, the default; clamped to the chunk); the outputs
+        are byte for byte the batch path's. Returns the previous value."""
+        return int(self.lib.blsv_set_tlock_lat_max(self._h, int(items)))
+
+    def tlock_lat_stats(self):
+        """(latency-path calls, U values they processed) since the context was created."""
+        a, b = ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(self.lib.blsv_tlock_lat_stats(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
+
     # ------------------------------------------------------------------ timelock sealing
     # include/blsverify.h "timelock": U_i = k_i G1 and K_i = B^k_i with B = e(pk, H(MessageV2(round)))^3
     # built once per (key, round); tlock_open(sigma_round, U_i) returns K_i.

@@ -383,8 +383,9 @@ int blsv_rlc_stats(blsv_ctx* ctx, uint64_t* groups, uint64_t* groups_failed, uin
  * pointer may be NULL.
  *
  * Sizing: the pipeline staging is used as it is (memory contract above, unchanged); more than a chunk
- * of items runs in chunk-sized passes with identical outputs. One lane per item serves every n: there
- * is no latency-path form and no service entry.
+ * of items runs in chunk-sized passes with identical outputs. One lane per item serves every n unless
+ * the latency-path form below is switched on (blsv_set_tlock_lat_max; off by default); there is no
+ * service entry.
  *
  * blsv_tlock_open_dev: d_us48 / d_out_gt576 (4-byte aligned) / d_reject_class (optional; 0 = opened)
  * are device pointers, sig96 is host memory. Sigma's decode class is read back (one 1-byte copy and
@@ -461,6 +462,47 @@ int blsv_tlock_open_rounds_dev(blsv_ctx* ctx, const uint8_t* sigs96, const uint6
                                uint8_t* d_reject_class /*optional*/, uint8_t* d_sig_class /*optional*/, void* stream);
 int blsv_tlock_open_rounds_stats(blsv_ctx* ctx, uint64_t* prepared, uint64_t* items);
 size_t blsv_set_tlock_dense_min(blsv_ctx* ctx, size_t items); /* returns the previous value */
+
+/*
+ * Opening on the latency path (opt-in). A client that holds one ciphertext, or a handful, when its round
+ * arrives pays on the batch path a serial chain of one-lane stages with the chip idle. The latency
+ * engine (latency contract above) has a timelock item too: one workgroup of eight waves per ciphertext
+ * decodes sigma and U side by side, runs the one pair's Miller loop beside their subgroup checks, then
+ * the final exponentiation and the encoding, in one launch (drand_amd/csrc/k_lat_tlock.hip).
+ *
+ * blsv_set_tlock_lat_max(ctx, L) returns the previous value. The default is 0 = off, or the environment
+ * variable BLSV_TLOCK_LAT_MAX (a non-negative integer; anything else is ignored with a note on stderr).
+ * L is clamped to the context's chunk, here and whenever the chunk shrinks (blsv_set_chunk, the
+ * out-of-memory halving). With L = 0 every entry point behaves exactly as described above.
+ *
+ * With L > 0 the HOST forms blsv_tlock_open and blsv_tlock_open_rounds send a call of 1 .. L items to the
+ * latency path (a call across rounds only while its signatures with a count of 0, which get a workgroup
+ * each, are no more than L too). Larger calls, n = 0 and both _dev forms take the paths above unchanged.
+ * Every output is byte for byte what the batch path returns for the same arguments: the BLSV_GT_LEN
+ * bytes (zeros for a rejected item), ok, reject_class, *sig_class / sig_class[j] (signatures with a count
+ * of 0 included), the class rule of an item under a sigma that does not decode, and for blsv_tlock_open
+ * BLSV_EINVAL with *sig_class set and no per-item output touched. Argument validation is each entry
+ * point's own, before the routing. Items that share a sigma each decode it again (that work runs beside
+ * their U decode), so nothing is prepared and nothing cached: the one-entry sigma cache survives a
+ * latency-path call under another sigma, and blsv_tlock_stats, blsv_tlock_open_rounds_stats and the
+ * sealing counters do not move. blsv_tlock_lat_stats: *launches = latency-path calls, *items = U values
+ * they processed (rejected ones included) since the context's creation; either pointer may be NULL.
+ *
+ * Memory: one device buffer of 96 m + 629 n bytes (+ 4 per item and per signature without items for a
+ * call across rounds) beside the pipeline staging, which this path does not touch.
+ *
+ * Measured on one MI355X (profiles/tlock_lat_bench.json; host forms, the two modes
+ * alternating call by call in one run, medians, identical bytes in every pair): a lone blsv_tlock_open
+ * whose sigma changes every call takes 1.51 ms against 18.28 ms on the batch path (12.1 times faster);
+ * under the same sigma every call, where the batch path has its cache hit, 1.50 ms against 14.33 ms (9.6
+ * times); 64 items of 64 distinct rounds in one blsv_tlock_open_rounds 1.54 ms against 16.70 ms (10.9
+ * times). One sigma, n items: 1.50 ms up to 16, 1.63 at 256 (one workgroup per compute unit), 3.20 at
+ * 512, 6.27 at 1,024, 12.24 at 2,048 and 24.06 at 4,096, against 14.3 falling to 12.3 - 12.5 ms on the
+ * batch path. The batch path is first faster at n = 4,096; at 2,048 the two are level. Recommended:
+ * blsv_set_tlock_lat_max(ctx, 2048), or 1024 where a call should win by a factor of two.
+ */
+size_t blsv_set_tlock_lat_max(blsv_ctx* ctx, size_t items); /* returns the previous value */
+int blsv_tlock_lat_stats(blsv_ctx* ctx, uint64_t* launches, uint64_t* items);
 
 /*
  * Sealing: the producing half, timelock.Encrypt(key.Pairing, G1 base, group key, MessageV2(round), msg)

@@ -432,6 +432,28 @@ int test_hostlogic() {
       out += "]";
     }
   }
+  {
+    // the timelock opening's latency path: routing, the plan of a call across rounds, the buffer layout
+    // (checked here only: nothing is added to the JSON)
+    CHECK(!tlock_lat_routes(0, 0, 4) && tlock_lat_routes(1, 0, 4) && tlock_lat_routes(4, 4, 4));
+    CHECK(!tlock_lat_routes(5, 0, 4) && !tlock_lat_routes(1, 5, 4) && !tlock_lat_routes(1, 0, 0));
+    const uint64_t counts[6] = {2, 0, 1, 3, 0, 0};
+    TlockLatPlan p;
+    CHECK(tlock_lat_plan(counts, 6, 3, p));
+    CHECK((p.sig_of == std::vector<uint32_t>{0, 0, 2, 3, 3, 3}) && (p.idle == std::vector<uint32_t>{1, 4, 5}));
+    CHECK(!tlock_lat_plan(counts, 6, 2, p) && p.idle.size() == 2);  // stops at the third idle signature
+    CHECK(tlock_lat_plan(counts, 0, 0, p) && p.sig_of.empty() && p.idle.empty());
+    for (size_t m : {size_t(1), size_t(6), size_t(1000)})
+      for (size_t n : {size_t(1), size_t(7), size_t(4096)})
+        for (size_t idle : {size_t(0), size_t(3)})
+          for (bool rounds : {false, true}) {
+            const TlockLatLayout l = tlock_lat_layout(m, n, rounds, idle);
+            CHECK(l.o_us == 96 * m && l.o_sigof == l.o_us + 48 * n && l.o_sigof % 4 == 0 && l.o_idle % 4 == 0);
+            CHECK(l.in_total == l.o_idle + 4 * idle && l.o_gt >= l.in_total && l.o_gt % 64 == 0);
+            CHECK(l.o_cls == l.o_gt + 576 * n && l.o_sigcls == l.o_cls + n && l.total == l.o_sigcls + m);
+            CHECK(l.out_total == l.total - l.o_gt);
+          }
+  }
   out += "]}}}";
   puts(out.c_str());
   return 0;

@@ -8,6 +8,9 @@
 //        wvtest verify  < lines "pk48 msg sig96" (hex)                -> reject class per line
 //        wvtest hash    < lines "msg" (hex)                            -> affine H(msg) raw hex
 //        wvtest pair    < lines "px py qx0 qx1 qy0 qy1" (affine raw)  -> Miller loop + final exp (raw)
+//        wvtest g1dec   < lines "u48" (hex)                            -> "class inf x y" (affine raw hex)
+//        wvtest topen   < lines "sig96 u48" (hex)                      -> sigma's class, the item's class, 576 bytes
+//        wvtest ttopen  < lines "sig96 u48", or "sig96 -"              -> the same by the eight-wave team
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
@@ -436,7 +439,97 @@ static int cmd_teamadd() {
   return 0;
 }
 
+// g1dec: "u48" -> "class inf x y" (affine raw hex; zeros unless the point decodes and is finite)
+static int cmd_g1dec() {
+  char c[300];
+  while (scanf("%299s", c) == 1) {
+    wv_init();
+    const auto u = unhex(c);
+    if (u.size() != 48) {
+      printf("%d 0 0 0\n", bls::REJ_LENGTH);
+      continue;
+    }
+    F x, y;
+    bool inf;
+    const int cls = g1_decompress(u.data(), x, y, inf);
+    if (cls || inf) {
+      printf("%d %d 0 0\n", cls, (int)inf);
+      continue;
+    }
+    const V rx = raw_canon(x), ry = raw_canon(y);
+    // the embedded form: the imaginary halves are zero
+    printf("0 0 %s %s%s\n", limbs_to_hex(rx, 0).c_str(), limbs_to_hex(ry, 0).c_str(),
+           limbs_to_hex(rx, 1) == "0" && limbs_to_hex(ry, 1) == "0" ? "" : " imaginary-half-nonzero");
+    fflush(stdout);
+  }
+  return 0;
+}
+
+static void print_topen(int sig_cls, int cls, const uint32_t (&out)[144]) {
+  printf("%d %d ", sig_cls, cls);
+  const uint8_t* b = (const uint8_t*)out;
+  for (int i = 0; i < 576; i++) printf("%02x", b[i]);
+  printf("\n");
+  fflush(stdout);
+}
+
+// topen: "sig96 u48" -> "sigma's class, the item's class, the 576 bytes" through wverify.h tlock_item
+static int cmd_topen() {
+  char a[300], b[300];
+  while (scanf("%299s %299s", a, b) == 2) {
+    wv_init();
+    const auto sig = unhex(a), u = unhex(b);
+    if (sig.size() != 96 || u.size() != 48) {
+      printf("%d %d -\n", bls::REJ_LENGTH, bls::REJ_LENGTH);
+      continue;
+    }
+    uint32_t out[144];
+    memset(out, 0xee, sizeof out);
+    uint8_t sc = 0xff;
+    const int cls = tlock_item(sig.data(), u.data(), out, sc);
+    print_topen(sc, cls, out);
+  }
+  return 0;
+}
+
+// ttopen: as topen, by the eight-wave team (wvteam.h tlock_team), one host thread per wave;
+// "sig96 -" classes the signature alone (sig_class_team) and prints "class - -"
+static int cmd_ttopen() {
+  char a[300], b[300];
+  while (scanf("%299s %299s", a, b) == 2) {
+    const auto sig = unhex(a), u = unhex(strcmp(b, "-") ? b : "");
+    const bool alone = !strcmp(b, "-");
+    if (sig.size() != 96 || (!alone && u.size() != 48)) {
+      printf("%d %d -\n", bls::REJ_LENGTH, bls::REJ_LENGTH);
+      continue;
+    }
+    for (auto& ctr : g_host_ctr) ctr.store(0);
+    uint32_t out[144];
+    memset(out, 0xee, sizeof out);
+    int cls[TEAM_WAVES], sc[TEAM_WAVES];
+    std::thread th[TEAM_WAVES];
+    for (int w = 0; w < TEAM_WAVES; w++)
+      th[w] = std::thread([&, w]() {
+        g_host_wave = w;
+        wv_init();
+        uint8_t s = 0xff;
+        cls[w] = alone ? 0 : tlock_team(sig.data(), u.data(), out, s);
+        if (alone) s = sig_class_team(sig.data());
+        sc[w] = s;
+      });
+    for (auto& t : th) t.join();
+    for (int w = 1; w < TEAM_WAVES; w++)
+      if (cls[w] != cls[0] || sc[w] != sc[0]) fprintf(stderr, "waves disagree\n"), abort();
+    if (alone) printf("%d - -\n", sc[0]), fflush(stdout);
+    else print_topen(sc[0], cls[0], out);
+  }
+  return 0;
+}
+
 int main(int argc, char** argv) {
+  if (argc >= 2 && !strcmp(argv[1], "g1dec")) return cmd_g1dec();
+  if (argc >= 2 && !strcmp(argv[1], "topen")) return cmd_topen();
+  if (argc >= 2 && !strcmp(argv[1], "ttopen")) return cmd_ttopen();
   if (argc >= 2 && !strcmp(argv[1], "field")) return cmd_field();
   if (argc >= 2 && !strcmp(argv[1], "inv")) return cmd_inv();
   if (argc >= 2 && !strcmp(argv[1], "teamadd")) return cmd_teamadd();
