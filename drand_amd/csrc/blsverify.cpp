@@ -40,6 +40,7 @@ int ensure_workspace(blsv_ctx* c, size_t cnt) {
     c->chunk = std::max(kMinChunk, ((want / 2) + 63) & ~size_t(63));
     c->lat_max = std::min(c->lat_max, c->chunk);
     c->tlock_lat.lat_max = std::min(c->tlock_lat.lat_max, c->chunk);
+    c->tseal_lat.lat_max = std::min(c->tseal_lat.lat_max, c->chunk);
     c->oom_halvings++;
   }
 }
@@ -118,6 +119,7 @@ int blsv_create(int device, blsv_ctx** out) {
   blsv_ctx* c = new blsv_ctx();
   c->device = device;
   c->tlock_lat.lat_max = std::min(tlock_lat_max_env(), c->chunk);
+  c->tseal_lat.lat_max = std::min(tseal_lat_max_env(), c->chunk);
   hipError_t e = hipSetDevice(device);
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking);
@@ -226,6 +228,21 @@ int blsv_tlock_lat_stats(blsv_ctx* c, uint64_t* launches, uint64_t* items) {
   return BLSV_OK;
 }
 
+// cutover of the timelock sealing's latency path (include/blsverify.h "timelock"; 0 = off)
+size_t blsv_set_tseal_lat_max(blsv_ctx* c, size_t items) {
+  if (!c) return 0;
+  const size_t prev = c->tseal_lat.lat_max;
+  c->tseal_lat.lat_max = std::min(items, c->chunk);
+  return prev;
+}
+
+int blsv_tseal_lat_stats(blsv_ctx* c, uint64_t* launches, uint64_t* items) {
+  if (!c) return BLSV_EINVAL;
+  if (launches) *launches = c->tseal_lat.launches;
+  if (items) *items = c->tseal_lat.items;
+  return BLSV_OK;
+}
+
 // per-context pass size (include/blsverify.h memory contract)
 size_t blsv_set_chunk(blsv_ctx* c, size_t items) {
   if (!c) return 0;
@@ -241,6 +258,7 @@ size_t blsv_set_chunk(blsv_ctx* c, size_t items) {
   c->chunk = v;
   c->lat_max = std::min(c->lat_max, v);
   c->tlock_lat.lat_max = std::min(c->tlock_lat.lat_max, v);
+  c->tseal_lat.lat_max = std::min(c->tseal_lat.lat_max, v);
   return prev;
 }
 

@@ -276,6 +276,24 @@ inline size_t tlock_lat_max_env() {
   return v;
 }
 
+// Cutover of the timelock sealing's latency path (blsv_set_tseal_lat_max): BLSV_TSEAL_LAT_MAX, parsed as
+// BLSV_TLOCK_LAT_MAX is, else 0 = off.
+inline size_t tseal_lat_max_env() {
+  static const size_t v = [] {
+    const char* e = getenv("BLSV_TSEAL_LAT_MAX");
+    if (!e) return size_t(0);
+    char* end = nullptr;
+    errno = 0;
+    const unsigned long long x = strtoull(e, &end, 10);
+    if (end == e || *end != '\0' || errno == ERANGE || e[0] == '-') {
+      fprintf(stderr, "blsverify: ignoring BLSV_TSEAL_LAT_MAX=\"%s\" (not a non-negative integer); it stays 0\n", e);
+      return size_t(0);
+    }
+    return (size_t)std::min<unsigned long long>(x, kMaxChunk);
+  }();
+  return v;
+}
+
 struct rlc_state {
   size_t group = kRlcGroupDefault;
   bool seed_pinned = false;  // blsv_test_rlc_seed
@@ -335,6 +353,18 @@ struct tlock_lat_state {
   DBuf buf;
   std::vector<uint8_t> up, down;
   TlockLatPlan plan;
+};
+
+// Timelock sealing on the latency path (blsv_set_tseal_lat_max, k_lat_tseal.hip): host calls of up to
+// lat_max items, one workgroup per item. Its own device buffer (hostlogic.h tseal_lat_layout), host staging
+// and counters; it reads T1 (tseal_state) and the key table TK (tsealr_state, through the key cache, whose
+// `keys` counter therefore counts a table whichever path built it). The base cache of tseal_state, the
+// sigma cache, the pipeline staging and every other counter stay as they are.
+struct tseal_lat_state {
+  size_t lat_max = 0;                // never above the chunk
+  uint64_t launches = 0, items = 0;  // blsv_tseal_lat_stats
+  DBuf buf;
+  std::vector<uint8_t> up, down;  // the scalars in `up` are cleared before the entry returns
 };
 
 struct blsv_ctx {
@@ -403,6 +433,7 @@ struct blsv_ctx {
   tsealr_state tsealr;
   tlockr_state tlockr;
   tlock_lat_state tlock_lat;
+  tseal_lat_state tseal_lat;
 };
 
 #define HIPCHK(ctx, expr)                                                             \

@@ -167,6 +167,15 @@ int tlock_lat_run(blsv_ctx* c, const uint8_t* sigs96, size_t m, const uint32_t* 
                   size_t n_idle, const uint8_t* us48, size_t n, TlockLatOut& o);
 void tlock_lat_copy_out(const TlockLatOut& o, size_t n, uint8_t* out_gt576, uint8_t* ok, uint8_t* reject_class);
 
+// ---- tsealr.cpp: T1 and the key table TK of pk48 behind the one-entry key cache (BLSV_EINVAL for a key that
+// does not decode or is the point at infinity, before anything else runs; no output is touched)
+int sealr_prepare(blsv_ctx* c, const uint8_t* pk48, size_t n, hipStream_t st);
+
+// ---- tseal_lat.cpp: a host call of n >= 1 items on the latency path (hostlogic.h tseal_lat_routes) under
+// the key pk48: item i to rounds[i], or every item to `round` when rounds is null
+int tseal_lat_run(blsv_ctx* c, const uint8_t* pk48, const uint64_t* rounds, uint64_t round, const uint8_t* scalars32,
+                  size_t n, uint8_t* out_us48, uint8_t* out_gt576, uint8_t* ok);
+
 // ---- tseal.cpp: the key a sealing call runs under -- pk48, or the group key (BLSV_ENOGROUP without one)
 int seal_key(blsv_ctx* c, const uint8_t* pk48, const uint8_t** key);
 

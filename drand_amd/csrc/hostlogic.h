@@ -450,5 +450,31 @@ inline TlockLatLayout tlock_lat_layout(size_t m, size_t n, bool rounds, size_t n
   return l;
 }
 
+// ---------------------------------------------------------------- timelock sealing on the latency path
+// blsv_set_tseal_lat_max: a host call of 1 .. lat_max items goes to k_lat_tseal, one workgroup per item.
+inline bool tseal_lat_routes(size_t n, size_t lat_max) { return n >= 1 && n <= lat_max; }
+// One device buffer per call: what the host uploads in one copy (for a call with a round per item the n
+// rounds, 8 bytes each, first: the buffer is 8-byte aligned; then the n scalars, 32 bytes each), then,
+// 64-byte aligned, what one download brings back (the n x 48 U bytes, the n x 576 Gt bytes, the n ok
+// bytes; both word arrays start 4-byte aligned). [o_scalars, in_total) is what the entry clears behind the
+// kernel. 665 bytes per item (657 for one shared round), plus at most 63 of padding.
+constexpr size_t kTsealLatBytesPerItem = 8 + BLSV_SCALAR_LEN + BLSV_U_LEN + BLSV_GT_LEN + 1;
+struct TsealLatLayout {
+  size_t o_rounds, o_scalars, in_total, o_us, o_gt, o_ok, out_total, total;
+};
+// false when a byte count of the n items does not fit size_t (l is then untouched)
+inline bool tseal_lat_layout(size_t n, bool rounds, TsealLatLayout& l) {
+  if (n > (SIZE_MAX - 63) / kTsealLatBytesPerItem) return false;
+  l.o_rounds = 0;
+  l.o_scalars = rounds ? 8 * n : 0;
+  l.in_total = l.o_scalars + BLSV_SCALAR_LEN * n;
+  l.o_us = (l.in_total + 63) & ~size_t(63);
+  l.o_gt = l.o_us + BLSV_U_LEN * n;
+  l.o_ok = l.o_gt + BLSV_GT_LEN * n;
+  l.out_total = BLSV_U_LEN * n + BLSV_GT_LEN * n + n;
+  l.total = l.o_us + l.out_total;
+  return true;
+}
+
 }  // namespace blsv_detail
 #pragma GCC visibility pop

@@ -189,6 +189,13 @@ void launch_lat_messages(const uint8_t* msgs, const uint64_t* off, const uint32_
 void launch_lat_tlock(const uint8_t* sigs, const uint32_t* sig_of, const uint8_t* us, size_t n_items,
                       const uint32_t* idle, size_t n_idle, uint8_t* out, uint8_t* cls, uint8_t* sig_cls,
                       hipStream_t st);
+// timelock sealing on the latency path (k_lat_tseal.hip): one workgroup per item, U_i = k_i G1 and
+// K_i = e(k_i pk, H(MessageV2(round_i)))^3 with round_i = rounds[i] (the one round `round` when rounds is
+// null) from the tables T1 and TK (kTsealT1Words words each: launch_tseal_g1_table, launch_tseal_key_table)
+// -> us (n x 48 bytes), gts (n x 576 bytes), both 4-byte aligned, and ok (n bytes); zeros and ok = 0 for a
+// scalar == 0 mod r
+void launch_lat_tseal(const uint32_t* T1, const uint32_t* TK, const uint64_t* rounds, uint64_t round,
+                      const uint8_t* scalars, size_t n, uint8_t* us, uint8_t* gts, uint8_t* ok, hipStream_t st);
 
 // ---- group / threshold / signing kernels (k_misc.hip)
 // decompress cnt G1 points (48 B each) -> pk table entries + inf flags + reject class

@@ -3,6 +3,7 @@
 // exponentiation -- and is cached with the table of its powers; then per pass U_i = k_i G1 and
 // K_i = B^k_i by table walks and the opening's Gt encoding, all in the pipeline staging (engine_ctx.h
 // lists which buffer holds what). The opening's sigma cache (tlock.cpp) is not touched.
+// With blsv_set_tseal_lat_max the host form hands calls of a few items to the latency path (tseal_lat.cpp).
 #include "host_internal.h"
 
 // The base's line table sits in LN behind the one-item park of the final exponentiation
@@ -127,6 +128,8 @@ int blsv_tlock_seal(blsv_ctx* c, const uint8_t* pk48, uint64_t round, const uint
   const uint8_t* key;
   int rc = seal_key(c, pk48, &key);
   if (rc) return rc;
+  if (tseal_lat_routes(n, std::min(c->tseal_lat.lat_max, c->chunk)))
+    return tseal_lat_run(c, key, nullptr, round, scalars32, n, out_us48, out_gt576, ok);
   rc = seal_prepare(c, key, round, n, c->stream);
   if (rc) return rc;
   if (!n) return BLSV_OK;

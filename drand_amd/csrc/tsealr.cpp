@@ -4,12 +4,14 @@
 // single-pair Miller passes of (P_i, H_i), the final exponentiation with its capture output and the
 // opening's Gt encoding, all in the pipeline staging (engine_ctx.h lists which buffer holds what). The
 // one-round base cache (tseal.cpp) and the opening's sigma cache (tlock.cpp) are not touched.
+// With blsv_set_tseal_lat_max the host form hands calls of a few items to the latency path (tseal_lat.cpp),
+// which builds the key table through sealr_prepare below.
 #include "host_internal.h"
 
 // Builds T1 once, and the key table unless pk48 is the cached key. The key's class is read back (the one
 // synchronisation of a call, and only on a new key); a key that does not decode or is the point at
-// infinity returns BLSV_EINVAL before anything else runs.
-static int sealr_prepare(blsv_ctx* c, const uint8_t* pk48, size_t n, hipStream_t st) {
+// infinity returns BLSV_EINVAL before anything else runs. Shared with the latency path (tseal_lat.cpp).
+int sealr_prepare(blsv_ctx* c, const uint8_t* pk48, size_t n, hipStream_t st) {
   tsealr_state& t = c->tsealr;
   if (t.valid && memcmp(t.pk, pk48, 48) == 0) return BLSV_OK;  // T1 was built with the entry
   int rc = ensure_workspace(c, std::max(n, size_t(1)));  // the call's passes find it allocated
@@ -124,6 +126,8 @@ int blsv_tlock_seal_rounds(blsv_ctx* c, const uint8_t* pk48, const uint64_t* rou
   const uint8_t* key;
   int rc = seal_key(c, pk48, &key);
   if (rc) return rc;
+  if (tseal_lat_routes(n, std::min(c->tseal_lat.lat_max, c->chunk)))
+    return tseal_lat_run(c, key, rounds, 0, scalars32, n, out_us48, out_gt576, ok);
   rc = sealr_prepare(c, key, n, c->stream);
   if (rc) return rc;
   if (!n) return BLSV_OK;

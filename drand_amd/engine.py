@@ -513,6 +513,18 @@ class Engine:
         self._check(self.lib.blsv_tlock_lat_stats(self._h, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value
 
+    def set_tseal_lat_max(self, items):
+        """blsv_set_tseal_lat_max: tlock_seal / tlock_seal_rounds calls of 1 .. items messages run on the
+        latency path, one workgroup per message (0 = off, the default; clamped to the chunk); the outputs
+        are byte for byte the batch path's. Returns the previous value."""
+        return int(self.lib.blsv_set_tseal_lat_max(self._h, int(items)))
+
+    def tseal_lat_stats(self):
+        """(latency-path sealing calls, scalars they processed) since the context was created."""
+        a, b = ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(self.lib.blsv_tseal_lat_stats(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
+
     # ------------------------------------------------------------------ timelock sealing
     # include/blsverify.h "timelock": U_i = k_i G1 and K_i = B^k_i with B = e(pk, H(MessageV2(round)))^3
     # built once per (key, round); tlock_open(sigma_round, U_i) returns K_i.

@@ -596,6 +596,58 @@ int blsv_tlock_seal_rounds_dev(blsv_ctx* ctx, const uint8_t* pk48, const uint64_
                                uint8_t* d_ok, void* stream);
 int blsv_tlock_seal_rounds_stats(blsv_ctx* ctx, uint64_t* keys, uint64_t* items);
 
+/*
+ * Sealing on the latency path (opt-in). The most common use of timelock encryption is one person locking
+ * one message to a future round; on the batch path that call pays a serial chain of one-lane stages with
+ * the chip idle. The latency engine has a sealing item too: one workgroup of eight waves per message
+ * hashes the item's round while two of its waves walk the tables of G1's and the key's multiples
+ * (U_i = k_i G1 compressed and stored, P_i = k_i pk), then runs the one pair's Miller loop e(P_i, H_i), the
+ * final exponentiation and the encoding, in one launch (drand_amd/csrc/k_lat_tseal.hip).
+ *
+ * blsv_set_tseal_lat_max(ctx, L) returns the previous value. The default is 0 = off, or the environment
+ * variable BLSV_TSEAL_LAT_MAX (a non-negative integer; anything else is ignored with a note on stderr).
+ * L is clamped to the context's chunk, here and whenever the chunk shrinks (blsv_set_chunk, the
+ * out-of-memory halving). It is a setter of its own, beside blsv_set_tlock_lat_max, because the two
+ * crossovers differ. With L = 0 every entry point behaves exactly as described above.
+ *
+ * With L > 0 the HOST forms blsv_tlock_seal and blsv_tlock_seal_rounds send a call of 1 .. L items to the
+ * latency path. Larger calls, n = 0 and both _dev forms take the paths above unchanged. Every output is
+ * byte for byte what the batch path returns for the same arguments: the BLSV_U_LEN and BLSV_GT_LEN bytes,
+ * ok, the zeros of a refused item, and BLSV_EINVAL / BLSV_ENOGROUP with no output touched. Argument
+ * validation is each entry point's own, before the routing. Items that share a round each hash it again
+ * (workgroups stay independent), so no base is built and none cached: the one-round base cache and the
+ * opening's prepared-signature cache survive a latency-path call.
+ *
+ * Key and counters: the path reads the table of G1's multiples and the key table of
+ * blsv_tlock_seal_rounds, through that entry's one-entry key cache (the same decode, the same BLSV_EINVAL;
+ * a new key costs its one table build and class read-back, the group key is stable). So
+ * blsv_tlock_seal_rounds_stats's *keys counts a table whichever path built it -- also one built for a
+ * latency-path blsv_tlock_seal -- while its *items, blsv_tlock_seal_stats and blsv_tlock_stats do not move
+ * on a latency-path call. blsv_tseal_lat_stats: *launches = latency-path calls, *items = scalars they
+ * processed (refused ones included) since the context's creation; either pointer may be NULL.
+ *
+ * Memory and secrecy: one device buffer of 665 bytes per item (8 round + 32 scalar bytes up, 48 + 576 + 1
+ * down; 657 for blsv_tlock_seal's one shared round; at most 63 bytes of padding) beside the pipeline
+ * staging, which this path does not touch. The staged scalars -- device and host copies -- are cleared
+ * behind the kernel before the entry returns, also when the call fails; a workgroup overwrites the
+ * on-chip copy of k_i pk before it exits. There is NO constant-time claim, as above.
+ *
+ * Measured on one MI355X (profiles/tseal_lat_bench.json; host forms, the two modes
+ * alternating call by call in one run, medians, identical bytes in every pair): a lone blsv_tlock_seal to a
+ * new round every call takes 1.88 ms against 34.48 ms on the batch path (18.4 times faster); to the same
+ * round every call, where the batch path has its cached base, 1.87 ms against 5.24 ms (2.8 times); 64 items
+ * of 64 distinct rounds in one blsv_tlock_seal_rounds 1.92 ms against 17.80 ms (9.3 times). n items: 1.87
+ * ms up to 16, 2.02 at 256 (one workgroup per compute unit), 3.97 at 512, 7.80 at 1,024, 15.24 at 2,048 and
+ * 30.10 at 4,096, through either entry point, against 5.2 - 6.1 ms for blsv_tlock_seal on a cached base and
+ * 17.8 - 20.1 ms for blsv_tlock_seal_rounds. The batch path is first faster at n = 1,024 for blsv_tlock_seal
+ * (at 512 the latency path still wins, 3.97 against 5.26 ms) and at n = 4,096 for blsv_tlock_seal_rounds
+ * (at 2,048 it wins by 1.2). Recommended: blsv_set_tseal_lat_max(ctx, 512), the bound that serves both
+ * entry points; 2048 for a caller that only seals across rounds. The two table walks take at most 580
+ * microseconds each with their conversions (measured alone), inside the hash's 926: off the critical path.
+ */
+size_t blsv_set_tseal_lat_max(blsv_ctx* ctx, size_t items); /* returns the previous value */
+int blsv_tseal_lat_stats(blsv_ctx* ctx, uint64_t* launches, uint64_t* items);
+
 /* ---------------------------------------------------------------- thread-safe service
  *
  * Concurrent single-item callers: the reference verifies each arrival in its own goroutine -- one per

@@ -454,6 +454,29 @@ int test_hostlogic() {
             CHECK(l.out_total == l.total - l.o_gt);
           }
   }
+  {
+    // the timelock sealing's latency path: routing and the buffer layout over the edge sizes, with its
+    // overflow guard (checked here only: nothing is added to the JSON)
+    CHECK(!tseal_lat_routes(0, 4) && tseal_lat_routes(1, 4) && tseal_lat_routes(4, 4));
+    CHECK(!tseal_lat_routes(5, 4) && !tseal_lat_routes(1, 0) && !tseal_lat_routes(0, 0));
+    static_assert(kTsealLatBytesPerItem == 665, "the header states the bytes per item");
+    for (size_t n : {size_t(1), size_t(2), size_t(7), size_t(9), size_t(64), size_t(65), size_t(4096), size_t(262144)})
+      for (bool rounds : {false, true}) {
+        TsealLatLayout l;
+        CHECK(tseal_lat_layout(n, rounds, l));
+        CHECK(l.o_rounds == 0 && l.o_scalars == (rounds ? 8 * n : 0) && l.in_total == l.o_scalars + 32 * n);
+        CHECK(l.o_us >= l.in_total && l.o_us - l.in_total < 64 && l.o_us % 64 == 0);
+        CHECK(l.o_gt == l.o_us + 48 * n && l.o_gt % 4 == 0 && l.o_ok == l.o_gt + 576 * n);
+        CHECK(l.out_total == 625 * n && l.total == l.o_ok + n && l.total == l.o_us + l.out_total);
+        CHECK(l.total <= kTsealLatBytesPerItem * n + 63);
+      }
+    TsealLatLayout big, keep;
+    const size_t most = (SIZE_MAX - 63) / kTsealLatBytesPerItem;
+    CHECK(tseal_lat_layout(most, true, big) && big.total >= big.o_ok && big.total > most);
+    keep = big;
+    CHECK(!tseal_lat_layout(most + 1, true, big) && !tseal_lat_layout(SIZE_MAX, false, big));
+    CHECK(big.total == keep.total && big.o_gt == keep.o_gt);  // untouched on overflow
+  }
   out += "]}}}";
   puts(out.c_str());
   return 0;

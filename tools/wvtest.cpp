@@ -11,6 +11,10 @@
 //        wvtest g1dec   < lines "u48" (hex)                            -> "class inf x y" (affine raw hex)
 //        wvtest topen   < lines "sig96 u48" (hex)                      -> sigma's class, the item's class, 576 bytes
 //        wvtest ttopen  < lines "sig96 u48", or "sig96 -"              -> the same by the eight-wave team
+//        wvtest tscalar < lines "k32" (hex)                            -> "ok k-mod-r digits" (tscalar.h)
+//        wvtest g1comp  < lines "x y" (affine raw hex), or "inf -"     -> the 48 compressed bytes (wseal.h)
+//        wvtest tseal   < lines "pk48 round k32" (round decimal)       -> "ok u48 gt576" (wseal.h seal_item)
+//        wvtest ttseal  < lines "pk48 round k32"                       -> the same by the eight-wave team
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
@@ -20,6 +24,8 @@
 
 #include "../drand_amd/csrc/wrecover.h"
 #include "../drand_amd/csrc/wvteam.h"
+#include "../drand_amd/csrc/wseal.h"
+#include "../drand_amd/csrc/tseal.h"
 
 #include <thread>
 
@@ -526,7 +532,135 @@ static int cmd_ttopen() {
   return 0;
 }
 
+// tscalar: "k32" -> "ok k digits": tscalar.h's reduction (k mod r as 64 hex digits, most significant
+// first) and its 64 four-bit digits, window 0 first
+static int cmd_tscalar() {
+  char a[300];
+  while (scanf("%299s", a) == 1) {
+    const auto kb = unhex(a);
+    if (kb.size() != 32) {
+      printf("- - -\n");
+      continue;
+    }
+    uint32_t k[8];
+    const bool ok = bls::tseal_scalar(kb.data(), k);
+    printf("%d ", (int)ok);
+    for (int w = 7; w >= 0; w--) printf("%08x", k[w]);
+    printf(" ");
+    for (int w = 0; w < bls::TSEAL_WINDOWS; w++) printf("%x", bls::tseal_digit(k, w));
+    printf("\n");
+  }
+  return 0;
+}
+
+static void print_hex(const uint8_t* b, int n) {
+  for (int i = 0; i < n; i++) printf("%02x", b[i]);
+}
+
+// g1comp: "x y" (affine, raw hex) or "inf -" -> the 48 bytes of wseal.h g1_compress_store. The point is
+// handed over in Jacobian form (x z^2, y z^3, z) with z = x + 1, so the conversion to affine runs too.
+static int cmd_g1comp() {
+  char a[300], b[300];
+  while (scanf("%299s %299s", a, b) == 2) {
+    wv_init();
+    G2J p = g2_infinity();
+    if (strcmp(a, "inf")) {
+      const F x = to_mont(raw_fp2(a, "0")), y = to_mont(raw_fp2(b, "0"));
+      const F z = lo_only(add(x, cst(WC_ONE2)));
+      const F zz = sqr2(z);
+      p = {dot(x, zz), dot(y, dot(zz, z)), z};
+    }
+    uint32_t out[12];
+    memset(out, 0xee, sizeof out);
+    g1_compress_store(out, p);
+    print_hex((const uint8_t*)out, 48);
+    printf("\n");
+    fflush(stdout);
+  }
+  return 0;
+}
+
+// the sealing tables in the batch engine's form, built by tseal.h's own row builder: T1 once, TK per key
+static std::vector<uint32_t> seal_table(const bls::g1a& A) {
+  std::vector<uint32_t> t((size_t)bls::TSEAL_T1_WORDS);
+  for (int w = 0; w < bls::TSEAL_WINDOWS; w++)
+    bls::tseal_g1_row_of(A, w, [&](int j, const bls::g1a& p) {
+      uint32_t* o = t.data() + (size_t)bls::tseal_entry(w, j) * bls::TSEAL_G1_WORDS;
+      for (int i = 0; i < 12; i++) o[i] = p.x.l[i], o[12 + i] = p.y.l[i];
+    });
+  return t;
+}
+static void round_b0(uint64_t round, uint32_t (&b0)[8]) {
+  uint32_t msg[8];
+  bls::drand_message_v2(msg, round);
+  xmd_b0_msg32(msg, b0);
+}
+
+// tseal / ttseal: "pk48 round k32" -> "ok u48 gt576" through wseal.h seal_item (one wave) or seal_team
+// (one host thread per wave); a key that does not decode, or is the point at infinity, prints "-1 - -"
+static int cmd_tseal(bool team) {
+  char a[300], b[300], c[300];
+  static const std::vector<uint32_t> T1 =
+      seal_table(bls::g1a{bls::fp_load_const(bls::G1_GEN_X), bls::fp_load_const(bls::G1_GEN_Y)});
+  std::string tk_key;
+  std::vector<uint32_t> TK;
+  while (scanf("%299s %299s %299s", a, b, c) == 3) {
+    const auto pk = unhex(a), kb = unhex(c);
+    const uint64_t round = strtoull(b, nullptr, 10);
+    if (tk_key != a) {
+      bls::g1a P;
+      bool pinf = false;
+      if (pk.size() != 48 || bls::g1_decompress(pk.data(), P, pinf) != bls::REJ_OK || pinf) {
+        printf("-1 - -\n");
+        continue;
+      }
+      TK = seal_table(P);
+      tk_key = a;
+    }
+    if (kb.size() != 32) {
+      printf("-1 - -\n");
+      continue;
+    }
+    uint32_t b0[8];
+    round_b0(round, b0);
+    uint32_t u[12], gt[144];
+    memset(u, 0xee, sizeof u);
+    memset(gt, 0xee, sizeof gt);
+    int ok[TEAM_WAVES];
+    if (!team) {
+      wv_init();
+      ok[0] = seal_item(kb.data(), b0, T1.data(), TK.data(), u, gt);
+    } else {
+      for (auto& ctr : g_host_ctr) ctr.store(0);
+      std::thread th[TEAM_WAVES];
+      for (int w = 0; w < TEAM_WAVES; w++)
+        th[w] = std::thread([&, w]() {
+          g_host_wave = w;
+          wv_init();
+          ok[w] = seal_team(kb.data(), b0, T1.data(), TK.data(), u, gt);
+        });
+      for (auto& t : th) t.join();
+      for (int w = 1; w < TEAM_WAVES; w++)
+        if (ok[w] != ok[0]) fprintf(stderr, "waves disagree\n"), abort();
+      // P's slots are overwritten before the workgroup exits
+      for (int i = 0; i < 64; i++)
+        if (g_host_blk[S_PX * 64 + i] | g_host_blk[S_PY * 64 + i]) fprintf(stderr, "P left in its slots\n"), abort();
+    }
+    printf("%d ", ok[0]);
+    print_hex((const uint8_t*)u, 48);
+    printf(" ");
+    print_hex((const uint8_t*)gt, 576);
+    printf("\n");
+    fflush(stdout);
+  }
+  return 0;
+}
+
 int main(int argc, char** argv) {
+  if (argc >= 2 && !strcmp(argv[1], "tscalar")) return cmd_tscalar();
+  if (argc >= 2 && !strcmp(argv[1], "g1comp")) return cmd_g1comp();
+  if (argc >= 2 && !strcmp(argv[1], "tseal")) return cmd_tseal(false);
+  if (argc >= 2 && !strcmp(argv[1], "ttseal")) return cmd_tseal(true);
   if (argc >= 2 && !strcmp(argv[1], "g1dec")) return cmd_g1dec();
   if (argc >= 2 && !strcmp(argv[1], "topen")) return cmd_topen();
   if (argc >= 2 && !strcmp(argv[1], "ttopen")) return cmd_ttopen();
