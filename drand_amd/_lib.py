@@ -34,6 +34,9 @@ REJ_PAIRING = 7
 REJ_SHARE_INDEX = 8
 REJ_TLOCK_SIG = 9
 
+KDF_SHA256_CTR = 1     # BLSV_KDF_SHA256_CTR: callers.kdf_sha256_ctr on the device
+TLOCK_MSG_MAX = 256    # BLSV_TLOCK_MSG_MAX: the longest message of blsv_tlock_decrypt* / blsv_tlock_encrypt*
+
 REJ_NAMES = {
     REJ_OK: "ok",
     REJ_LENGTH: "bad length",
@@ -127,6 +130,15 @@ SIGNATURES = {
     "blsv_tlock_seal_rounds": (ctypes.c_int, [vp, u8p, u64p, u8p, sz, u8p, u8p, u8p]),
     "blsv_tlock_seal_rounds_dev": (ctypes.c_int, [vp, u8p, vp, vp, sz, vp, vp, vp, vp]),
     "blsv_tlock_seal_rounds_stats": (ctypes.c_int, [vp, u64p, u64p]),
+    "blsv_tlock_decrypt": (ctypes.c_int, [vp, u8p, u8p, u8p, sz, sz, ctypes.c_int, u8p, u8p, u8p, u8p]),
+    "blsv_tlock_decrypt_dev": (ctypes.c_int, [vp, u8p, vp, vp, sz, sz, ctypes.c_int, vp, vp, vp]),
+    "blsv_tlock_decrypt_rounds": (ctypes.c_int, [vp, u8p, u64p, sz, u8p, u8p, sz, sz, ctypes.c_int, u8p, u8p, u8p,
+                                                  u8p]),
+    "blsv_tlock_decrypt_rounds_dev": (ctypes.c_int, [vp, u8p, u64p, sz, vp, vp, sz, sz, ctypes.c_int, vp, vp, vp, vp]),
+    "blsv_tlock_encrypt": (ctypes.c_int, [vp, u8p, ctypes.c_uint64, u8p, u8p, sz, sz, ctypes.c_int, u8p, u8p, u8p]),
+    "blsv_tlock_encrypt_dev": (ctypes.c_int, [vp, u8p, ctypes.c_uint64, vp, vp, sz, sz, ctypes.c_int, vp, vp, vp, vp]),
+    "blsv_tlock_encrypt_rounds": (ctypes.c_int, [vp, u8p, u64p, u8p, u8p, sz, sz, ctypes.c_int, u8p, u8p, u8p]),
+    "blsv_tlock_encrypt_rounds_dev": (ctypes.c_int, [vp, u8p, vp, vp, vp, sz, sz, ctypes.c_int, vp, vp, vp, vp]),
 }
 
 _lib = None

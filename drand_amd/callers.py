@@ -436,6 +436,124 @@ def timelock_seal_rounds(engine, items, kdf: Callable[[bytes, int], bytes], scal
     return out
 
 
+# Timelock in one call (include/blsverify.h "timelock in one call"): the four functions above under
+# ``kdf_sha256_ctr`` with the key stream and the XOR done on the device, so that a call moves len(C) bytes
+# per item instead of 576 and Python hashes nothing. The engine takes one message length per call: ragged
+# lengths are padded with zeros to the call's longest and every result is cut back to its own length (the
+# key stream is prefix-stable, so the bytes are those of the per-length result). A call with a message
+# longer than ``TLOCK_MSG_MAX`` bytes or an empty one, or with nothing to do, goes through the function
+# above with ``kdf_sha256_ctr``: the bytes are the same.
+
+def _fused(lengths) -> int:
+    """The padded length of a call the fused entry points take, or 0 for one that goes the long way."""
+    from ._lib import TLOCK_MSG_MAX
+    lengths = list(lengths)
+    if not lengths or min(lengths) == 0 or max(lengths) > TLOCK_MSG_MAX:
+        return 0
+    return max(lengths)
+
+
+def timelock_decrypt(engine, round_: int, sig_v2: bytes, ciphertexts, verify: bool = True) -> list:
+    """``timelock_open(engine, round_, sig_v2, ciphertexts, kdf_sha256_ctr, verify)`` in one engine call
+    (``Engine.tlock_decrypt``): the plaintext per ``(U48, C)``, or ``None`` where U did not decode (a
+    wrong-length U is rejected host-side). ``verify`` is ``timelock_open``'s."""
+    sig_v2 = bytes(sig_v2)
+    cts = [(bytes(u), bytes(c)) for u, c in ciphertexts]
+    good = [k for k, (u, _) in enumerate(cts) if len(u) == 48]
+    mlen = _fused(len(cts[k][1]) for k in good)
+    if not mlen:
+        return timelock_open(engine, round_, sig_v2, cts, kdf_sha256_ctr, verify=verify)
+    if verify:
+        if len(sig_v2) != SIG_LEN:
+            raise VerifyError(round_, "bad length")
+        res = engine.verify_unchained([sig_v2], first_round=round_)
+        if not res.ok[0]:
+            from ._lib import REJ_NAMES
+            raise VerifyError(round_, REJ_NAMES.get(res.reject_class[0], "bls: invalid signature"))
+    res = engine.tlock_decrypt(sig_v2, [cts[k][0] for k in good], [cts[k][1].ljust(mlen, b"\0") for k in good])
+    out = [None] * len(cts)
+    for k, m in zip(good, res.msgs):
+        out[k] = None if m is None else m[:len(cts[k][1])]
+    return out
+
+
+def timelock_decrypt_rounds(engine, rounds, verify: bool = True) -> list:
+    """``timelock_open_rounds(engine, rounds, kdf_sha256_ctr, verify)`` in one engine call
+    (``Engine.tlock_decrypt_rounds``): one list of plaintexts per ``(round, sig_v2, [(U48, C), ...])``."""
+    rounds = [(int(r), bytes(s), [(bytes(u), bytes(c)) for u, c in cts]) for r, s, cts in rounds]
+    good = [[k for k, (u, _) in enumerate(cts) if len(u) == 48] for _, _, cts in rounds]
+    mlen = _fused(len(cts[k][1]) for (_, _, cts), g in zip(rounds, good) for k in g)
+    if not mlen:
+        return timelock_open_rounds(engine, rounds, kdf_sha256_ctr, verify=verify)
+    if verify:
+        from ._lib import REJ_NAMES
+        for r, s, _ in rounds:
+            if len(s) != SIG_LEN:
+                raise VerifyError(r, "bad length")
+        res = engine.verify_unchained([s for _, s, _ in rounds], rounds=[r for r, _, _ in rounds])
+        for (r, _, _), ok, cls in zip(rounds, res.ok, res.reject_class):
+            if not ok:
+                raise VerifyError(r, REJ_NAMES.get(cls, "bls: invalid signature"))
+    res = engine.tlock_decrypt_rounds([s for _, s, _ in rounds],
+                                      [[cts[k][0] for k in g] for (_, _, cts), g in zip(rounds, good)],
+                                      [[cts[k][1].ljust(mlen, b"\0") for k in g] for (_, _, cts), g in zip(rounds, good)])
+    out, at = [], 0
+    for (_, _, cts), g in zip(rounds, good):
+        opened = [None] * len(cts)
+        for k in g:
+            m = res.msgs[at]
+            at += 1
+            opened[k] = None if m is None else m[:len(cts[k][1])]
+        out.append(opened)
+    return out
+
+
+def timelock_encrypt(engine, round_: int, messages, scalars=None, pk48=None) -> list:
+    """``timelock_seal(engine, round_, messages, kdf_sha256_ctr, scalars, pk48)`` in one engine call
+    (``Engine.tlock_encrypt``): a list of ``(U48, C)``. The Gt values never reach the host."""
+    msgs = [bytes(m) for m in messages]
+    mlen = _fused(len(m) for m in msgs)
+    if scalars is None:
+        import secrets
+        from .engine import R_ORDER
+        scalars = [secrets.randbelow(R_ORDER - 1) + 1 for _ in msgs]
+    scalars = list(scalars)
+    if not mlen:
+        return timelock_seal(engine, round_, msgs, kdf_sha256_ctr, scalars=scalars, pk48=pk48)
+    if len(scalars) != len(msgs):
+        raise ValueError("%d scalars for %d messages" % (len(scalars), len(msgs)))
+    res = engine.tlock_encrypt(round_, scalars, [m.ljust(mlen, b"\0") for m in msgs], pk48=pk48)
+    out = []
+    for k, (m, ok, u, c) in enumerate(zip(msgs, res.ok, res.us, res.cs)):
+        if not ok:
+            raise ValueError("scalar %d is 0 mod r: nothing can be sealed under it" % k)
+        out.append((u, c[:len(m)]))
+    return out
+
+
+def timelock_encrypt_rounds(engine, items, scalars=None, pk48=None) -> list:
+    """``timelock_seal_rounds(engine, items, kdf_sha256_ctr, scalars, pk48)`` in one engine call
+    (``Engine.tlock_encrypt_rounds``): a list of ``(U48, C)`` in the order of ``items``."""
+    items = [(int(r), bytes(m)) for r, m in items]
+    mlen = _fused(len(m) for _, m in items)
+    if scalars is None:
+        import secrets
+        from .engine import R_ORDER
+        scalars = [secrets.randbelow(R_ORDER - 1) + 1 for _ in items]
+    scalars = list(scalars)
+    if not mlen:
+        return timelock_seal_rounds(engine, items, kdf_sha256_ctr, scalars=scalars, pk48=pk48)
+    if len(scalars) != len(items):
+        raise ValueError("%d scalars for %d messages" % (len(scalars), len(items)))
+    res = engine.tlock_encrypt_rounds([r for r, _ in items], scalars, [m.ljust(mlen, b"\0") for _, m in items], pk48=pk48)
+    out = []
+    for k, ((_, m), ok, u, c) in enumerate(zip(items, res.ok, res.us, res.cs)):
+        if not ok:
+            raise ValueError("scalar %d is 0 mod r: nothing can be sealed under it" % k)
+        out.append((u, c[:len(m)]))
+    return out
+
+
 # --------------------------------------------------------------------------------------------------
 # Threshold aggregation (SURVEY.md §8a row a17): chainStore.runAggregator (chain/beacon/chain.go:91-190)
 # and its partialCache / roundCache (chain/beacon/cache.go:18-182), restated. The cache, the gate and

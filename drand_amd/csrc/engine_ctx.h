@@ -1,5 +1,5 @@
 // Internal to libblsverify.so (never installed, no C ABI): the context object and the helpers the
-// C-ABI entry points (blsverify.cpp, verify.cpp, threshold.cpp, tlock.cpp, tlockr.cpp, tseal.cpp, tsealr.cpp, testhooks.cpp; their shared
+// C-ABI entry points (blsverify.cpp, verify.cpp, threshold.cpp, tlock.cpp, tlockr.cpp, tseal.cpp, tsealr.cpp, tcrypt.cpp, testhooks.cpp; their shared
 // internals are host_internal.h) and the thread-safe service (service.cpp) share.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -131,6 +131,21 @@ static_assert(blsk::FEXP_PARK_WORDS(kMaxChunk) <= blsk::MILLER_LINE_WORDS * kMax
               "opening across rounds: the park does not fit LN behind the f pass");
 static_assert(2 + 4 + 4 + 4 * blsk::kTlockTileWords <= 4 * 3 * blsk::F_WORDS,
               "opening across rounds: the signatures' flags and the plan of a pass do not fit the FW staging");
+
+// Timelock in one call (blsv_tlock_decrypt* / blsv_tlock_encrypt*, tcrypt.cpp, k_tmask.hip): each of the four
+// timelock passes above with its last stage swapped -- k_tmask reads the captured values in HQ where
+// k_tlock_encode read them, and nothing else in the pass moves. What a host form stages for a pass of cnt items
+// of mlen bytes:
+//   F          free behind the final exponentiation (the encoded bytes used to come back through it): the
+//              cnt x mlen input bytes (ciphertexts, or plaintexts) at its start, uploaded behind the
+//              exponentiation, and the cnt x mlen output bytes behind them, from where the download takes them
+//              with the class / ok bytes of the pass it runs. An encrypting pass clears the input part behind
+//              the kernel
+//   HQ         the captured values, as ever; an encrypting pass (host or device form) clears the cnt x 576
+//              bytes of K behind the mask kernel, also when the pass failed
+// A device form reads and writes the caller's buffers in place. No storage of its own.
+static_assert(2 * BLSV_TLOCK_MSG_MAX <= 4 * blsk::F_WORDS,
+              "timelock in one call: a pass's input and output bytes do not fit the F staging");
 
 struct DBuf {
   void* p = nullptr;

@@ -1,5 +1,5 @@
 // Internal to the HIP-side host units of libblsverify.so (blsverify.cpp, verify.cpp, threshold.cpp,
-// tlock.cpp, tlockr.cpp, tseal.cpp, tsealr.cpp, testhooks.cpp): the pinned small copies, stage timing, the typed view of the pipeline
+// tlock.cpp, tlockr.cpp, tseal.cpp, tsealr.cpp, tcrypt.cpp, testhooks.cpp): the pinned small copies, stage timing, the typed view of the pipeline
 // staging with its launch wrappers, and the one pass loop every verification entry point runs.
 #pragma once
 #include <functional>
@@ -157,15 +157,38 @@ int decode_g1(blsv_ctx* c, const uint8_t* pk48, size_t cnt, DBuf& tab, DBuf& inf
 // n messages packed back to back (msg_lens[i] bytes each) into in_msgs / in_off / in_len
 int upload_messages(blsv_ctx* c, const uint8_t* msgs, const uint32_t* msg_lens, size_t n);
 
+// ---- tcrypt.cpp: the fused tail of the four timelock passes (blsv_tlock_decrypt* / blsv_tlock_encrypt*,
+// k_tmask.hip). mlen == 0: no mask tail, the pass ends in the Gt encoding as ever.
+struct MaskTail {
+  size_t mlen = 0;
+  bool host = false;    // a host form: the pass's input and output bytes are staged in F (engine_ctx.h)
+  bool secret = false;  // encrypt: the captured K and the staged plaintexts are cleared behind the kernel
+};
+// Where a host form's pass of cnt items leaves its output on the device: F behind the staged input with a
+// mask tail, else the start of F
+uint8_t* mask_host_out(const blsv_ctx* c, const MaskTail& mk, size_t cnt);
+// The tail of a pass of cnt items whose values are captured in HQ: in = the pass's cnt x mlen input bytes
+// (host memory for a host form, uploaded to F here; else device memory), d_out = cnt x mlen bytes on the
+// device; flag[i] == good marks an item with a value
+int mask_tail(blsv_ctx* c, const MaskTail& mk, const uint8_t* flag, uint8_t good, size_t cnt, const uint8_t* in,
+              uint8_t* d_out, hipStream_t st);
+// Behind the tail of an encrypting pass, also when it failed: clears the K capture in HQ and a host form's
+// staged plaintexts in F
+hipError_t mask_wipe(blsv_ctx* c, const MaskTail& mk, size_t cnt, hipStream_t st);
+
 // ---- tlock.cpp: a host call of n >= 1 items on the latency path (hostlogic.h tlock_lat_routes). The m
 // signatures, item i under sig_of[i] (null: all under signature 0), the n_idle signatures idle[] classed
 // alone. o points into the context's host staging, valid until the next call; copy_out hands the items over.
+// A decrypting call (mlen != 0) also passes its n x mlen ciphertext bytes cs: the mask kernel runs behind the
+// latency kernel and o.gt points to the n x mlen masked bytes instead (copy_out's out_len = mlen).
 struct TlockLatOut {
   const uint8_t *gt, *cls, *sig_cls;  // n x 576 bytes, n item classes, m signature classes
 };
 int tlock_lat_run(blsv_ctx* c, const uint8_t* sigs96, size_t m, const uint32_t* sig_of, const uint32_t* idle,
-                  size_t n_idle, const uint8_t* us48, size_t n, TlockLatOut& o);
-void tlock_lat_copy_out(const TlockLatOut& o, size_t n, uint8_t* out_gt576, uint8_t* ok, uint8_t* reject_class);
+                  size_t n_idle, const uint8_t* us48, size_t n, TlockLatOut& o, const uint8_t* cs = nullptr,
+                  size_t mlen = 0);
+void tlock_lat_copy_out(const TlockLatOut& o, size_t n, uint8_t* out, uint8_t* ok, uint8_t* reject_class,
+                        size_t out_len = BLSV_GT_LEN);
 
 // ---- tsealr.cpp: T1 and the key table TK of pk48 behind the one-entry key cache (BLSV_EINVAL for a key that
 // does not decode or is the point at infinity, before anything else runs; no output is touched)
@@ -173,8 +196,10 @@ int sealr_prepare(blsv_ctx* c, const uint8_t* pk48, size_t n, hipStream_t st);
 
 // ---- tseal_lat.cpp: a host call of n >= 1 items on the latency path (hostlogic.h tseal_lat_routes) under
 // the key pk48: item i to rounds[i], or every item to `round` when rounds is null
+// An encrypting call (mlen != 0) also passes its n x mlen message bytes: the mask kernel runs behind the
+// latency kernel and `out` receives the n x mlen ciphertext bytes instead of the n x 576 Gt bytes.
 int tseal_lat_run(blsv_ctx* c, const uint8_t* pk48, const uint64_t* rounds, uint64_t round, const uint8_t* scalars32,
-                  size_t n, uint8_t* out_us48, uint8_t* out_gt576, uint8_t* ok);
+                  size_t n, uint8_t* out_us48, uint8_t* out, uint8_t* ok, const uint8_t* msgs = nullptr, size_t mlen = 0);
 
 // ---- tseal.cpp: the key a sealing call runs under -- pk48, or the group key (BLSV_ENOGROUP without one)
 int seal_key(blsv_ctx* c, const uint8_t* pk48, const uint8_t** key);

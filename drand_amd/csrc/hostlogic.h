@@ -298,6 +298,13 @@ inline SealRoundsLayout seal_rounds_layout(size_t cnt) {
   return l;
 }
 
+// blsv_tlock_decrypt* / blsv_tlock_encrypt*: whether the call's KDF and message length are ones the fused
+// tail knows, and the byte counts of n items of mlen bytes fit size_t
+inline bool tcrypt_fits(int kdf, size_t mlen, size_t n) {
+  return kdf == BLSV_KDF_SHA256_CTR && mlen >= 1 && mlen <= BLSV_TLOCK_MSG_MAX && n <= SIZE_MAX / BLSV_TLOCK_MSG_MAX &&
+         n <= SIZE_MAX / BLSV_GT_LEN;
+}
+
 // ---------------------------------------------------------------- blsv_tlock_open_rounds*: the plan
 // m round signatures, round j owning counts[j] consecutive items of the n packed ones. Whether the call's
 // arguments are consistent and every byte count of it fits size_t: sum counts == n (the sum itself must
@@ -432,21 +439,27 @@ inline bool tlock_lat_plan(const uint64_t* counts, size_t m, size_t max_idle, Tl
 // One device buffer per call: what the host uploads in one copy (the m signatures, the n compressed U, and
 // for a call across rounds sig_of and idle), then, 64-byte aligned, what one download brings back (the n x
 // 576 bytes, the n item classes, the m signature classes). Every offset of a word array is 4-byte aligned.
+// A decrypting call (mbytes = n x mlen, else 0) also uploads its mbytes ciphertext bytes, behind idle, and
+// keeps its mbytes output bytes between the Gt bytes and the classes: its download starts there (o_down)
+// and leaves the Gt bytes on the device. With mbytes = 0 nothing moves.
 struct TlockLatLayout {
-  size_t o_sigs, o_us, o_sigof, o_idle, in_total, o_gt, o_cls, o_sigcls, out_total, total;
+  size_t o_sigs, o_us, o_sigof, o_idle, o_min, in_total, o_gt, o_mout, o_cls, o_sigcls, o_down, out_total, total;
 };
-inline TlockLatLayout tlock_lat_layout(size_t m, size_t n, bool rounds, size_t n_idle) {
+inline TlockLatLayout tlock_lat_layout(size_t m, size_t n, bool rounds, size_t n_idle, size_t mbytes = 0) {
   TlockLatLayout l;
   l.o_sigs = 0;
   l.o_us = 96 * m;
   l.o_sigof = l.o_us + BLSV_U_LEN * n;
   l.o_idle = l.o_sigof + (rounds ? 4 * n : 0);
-  l.in_total = l.o_idle + 4 * n_idle;
+  l.o_min = l.o_idle + 4 * n_idle;
+  l.in_total = l.o_min + mbytes;
   l.o_gt = (l.in_total + 63) & ~size_t(63);
-  l.o_cls = l.o_gt + BLSV_GT_LEN * n;
+  l.o_mout = l.o_gt + BLSV_GT_LEN * n;
+  l.o_cls = l.o_mout + mbytes;
   l.o_sigcls = l.o_cls + n;
-  l.out_total = BLSV_GT_LEN * n + n + m;
-  l.total = l.o_gt + l.out_total;
+  l.o_down = mbytes ? l.o_mout : l.o_gt;
+  l.out_total = l.o_sigcls + m - l.o_down;
+  l.total = l.o_sigcls + m;
   return l;
 }
 
@@ -459,19 +472,24 @@ inline bool tseal_lat_routes(size_t n, size_t lat_max) { return n >= 1 && n <= l
 // bytes; both word arrays start 4-byte aligned). [o_scalars, in_total) is what the entry clears behind the
 // kernel. 665 bytes per item (657 for one shared round), plus at most 63 of padding.
 constexpr size_t kTsealLatBytesPerItem = 8 + BLSV_SCALAR_LEN + BLSV_U_LEN + BLSV_GT_LEN + 1;
+// An encrypting call (mlen > 0, else 0) also uploads its n x mlen message bytes, behind the scalars and
+// cleared with them, and keeps its n x mlen ciphertext bytes between the Gt bytes and the ok bytes: it
+// downloads the U bytes, and from o_mout on, and leaves the Gt bytes on the device. With mlen = 0 nothing moves.
 struct TsealLatLayout {
-  size_t o_rounds, o_scalars, in_total, o_us, o_gt, o_ok, out_total, total;
+  size_t o_rounds, o_scalars, o_min, in_total, o_us, o_gt, o_mout, o_ok, out_total, total;
 };
 // false when a byte count of the n items does not fit size_t (l is then untouched)
-inline bool tseal_lat_layout(size_t n, bool rounds, TsealLatLayout& l) {
-  if (n > (SIZE_MAX - 63) / kTsealLatBytesPerItem) return false;
+inline bool tseal_lat_layout(size_t n, bool rounds, TsealLatLayout& l, size_t mlen = 0) {
+  if (mlen > BLSV_TLOCK_MSG_MAX || n > (SIZE_MAX - 63) / (kTsealLatBytesPerItem + 2 * mlen)) return false;
   l.o_rounds = 0;
   l.o_scalars = rounds ? 8 * n : 0;
-  l.in_total = l.o_scalars + BLSV_SCALAR_LEN * n;
+  l.o_min = l.o_scalars + BLSV_SCALAR_LEN * n;
+  l.in_total = l.o_min + mlen * n;
   l.o_us = (l.in_total + 63) & ~size_t(63);
   l.o_gt = l.o_us + BLSV_U_LEN * n;
-  l.o_ok = l.o_gt + BLSV_GT_LEN * n;
-  l.out_total = BLSV_U_LEN * n + BLSV_GT_LEN * n + n;
+  l.o_mout = l.o_gt + BLSV_GT_LEN * n;
+  l.o_ok = l.o_mout + mlen * n;
+  l.out_total = l.o_ok + n - l.o_us;
   l.total = l.o_us + l.out_total;
   return true;
 }

@@ -169,6 +169,18 @@ void launch_miller_lines1(const uint32_t* P, const uint32_t* H, const uint8_t* h
 void launch_miller_f1(const uint32_t* LN, const uint8_t* h_inf, const uint8_t* cls, size_t cnt, uint32_t* F,
                       hipStream_t st);
 
+// ---- timelock encrypt / decrypt, the fused tail (k_tmask.hip, tmask.h): one lane per item,
+// out[i] = in[i] XOR kdf_sha256_ctr(Gt value of item i, mlen) over cnt x mlen packed bytes (1 <= mlen <= 256, no
+// alignment asked for: dwords move only when in, out and mlen are all multiples of 4), or mlen zero bytes
+// where flag[i] != good (class bytes: good = 0; ok bytes: good = 1). Nothing outside [i mlen, (i + 1) mlen) is
+// written; out == in is allowed. tmask: E = the captured values (SoA of stride cnt, what launch_tlock_encode
+// reads). tmask_encoded: gt576 = cnt x 576 encoded bytes, 4-byte aligned (what the latency kernels write).
+constexpr size_t kTmaskMsgMax = 256;
+void launch_tmask(const uint32_t* E, const uint8_t* flag, uint8_t good, size_t cnt, const uint8_t* in, uint8_t* out,
+                  size_t mlen, hipStream_t st);
+void launch_tmask_encoded(const uint8_t* gt576, const uint8_t* flag, uint8_t good, size_t cnt, const uint8_t* in,
+                          uint8_t* out, size_t mlen, hipStream_t st);
+
 // ---- latency path (k_lat.hip): one workgroup per item, the whole verification; writes cls[i] (REJ_*)
 int lat_trace_read(uint64_t* out, int n, hipStream_t st);  // phase marks of item 0 (wteam.h WV_MARK)
 int lat_trace_clear(hipStream_t st);

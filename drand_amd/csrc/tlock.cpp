@@ -40,9 +40,11 @@ static int tlock_prepare_sig(blsv_ctx* c, const uint8_t* sig96, hipStream_t st, 
   return BLSV_OK;
 }
 
-// One pass of cnt <= cap items: d_us (cnt x 48 bytes) -> d_out (cnt x 576 bytes), classes in s_inf
-static int tlock_pass(blsv_ctx* c, const uint8_t* d_us, size_t cnt, uint8_t* d_out, uint8_t* d_cls_out,
-                      hipStream_t st) {
+// One pass of cnt <= cap items: d_us (cnt x 48 bytes) -> d_out (cnt x 576 bytes), classes in s_inf. With a
+// mask tail (mk.mlen != 0; blsv_tlock_decrypt*) the encoding is replaced by the mask kernel over the pass's
+// input bytes mk_in: d_out gets cnt x mlen bytes.
+static int tlock_pass(blsv_ctx* c, const uint8_t* d_us, size_t cnt, uint8_t* d_out, uint8_t* d_cls_out, hipStream_t st,
+                      const MaskTail& mk = MaskTail(), const uint8_t* mk_in = nullptr) {
   const tlock_state& t = c->tlock;
   const Staging w = staging(c);
   uint32_t* U = w.H;
@@ -63,7 +65,12 @@ static int tlock_pass(blsv_ctx* c, const uint8_t* d_us, size_t cnt, uint8_t* d_o
     // the values are captured in HQ, so the park stays in LN (a timelock pass stages no lines)
     blsk::launch_final_exp(w.F, w.FW, cnt, 0, cnt, w.cls, st, w.LN, w.HQ);
   }
-  blsk::launch_tlock_encode(w.HQ, ucls, cnt, d_out, st);
+  if (mk.mlen) {
+    const int rc = mask_tail(c, mk, ucls, BLSV_REJ_OK, cnt, mk_in, d_out, st);
+    if (rc) return rc;
+  } else {
+    blsk::launch_tlock_encode(w.HQ, ucls, cnt, d_out, st);
+  }
   if (d_cls_out) HIPCHK(c, hipMemcpyAsync(d_cls_out, ucls, cnt, hipMemcpyDeviceToDevice, st));
   HIPCHK(c, hipGetLastError());
   return BLSV_OK;
@@ -72,21 +79,26 @@ static int tlock_pass(blsv_ctx* c, const uint8_t* d_us, size_t cnt, uint8_t* d_o
 // Every pass of n items under the prepared sigma. Device buffers (host == false): us, out and cls
 // (optional) are read and written in place on st. Host buffers: a pass's compressed U bytes travel in
 // S, its encoded values come back through F, and each pass ends with the download's synchronisation.
-static int tlock_passes(blsv_ctx* c, bool host, const uint8_t* us, size_t n, uint8_t* out, uint8_t* cls,
-                        hipStream_t st) {
+// With a mask tail, mk_in is the call's n x mlen input bytes and out receives n x mlen bytes; a host call's
+// pass stages both in F (mask_tail).
+static int tlock_passes(blsv_ctx* c, bool host, const uint8_t* us, size_t n, uint8_t* out, uint8_t* cls, hipStream_t st,
+                        const MaskTail& mk = MaskTail(), const uint8_t* mk_in = nullptr) {
   int rc = ensure_workspace(c, n);
   if (rc) return rc;
+  const size_t out_len = mk.mlen ? mk.mlen : BLSV_GT_LEN;
   for (size_t base = 0; base < n; base += c->cap) {
     const size_t cnt = std::min(c->cap, n - base);
     const uint8_t* pass_us = us + base * BLSV_U_LEN;
-    uint8_t* pass_out = out + base * BLSV_GT_LEN;
+    const uint8_t* pass_in = mk.mlen ? mk_in + base * mk.mlen : nullptr;
+    uint8_t* pass_out = out + base * out_len;
     if (host) {
+      uint8_t* d_out = mask_host_out(c, mk, cnt);
       HIPCHK(c, h2d(c, c->S.p, pass_us, cnt * BLSV_U_LEN));
-      rc = tlock_pass(c, c->S.as<uint8_t>(), cnt, c->F.as<uint8_t>(), nullptr, st);
+      rc = tlock_pass(c, c->S.as<uint8_t>(), cnt, d_out, nullptr, st, mk, pass_in);
       if (rc) return rc;
-      HIPCHK(c, download_sync(c, {{pass_out, c->F.p, cnt * BLSV_GT_LEN}, {cls + base, c->s_inf.p, cnt}}));
+      HIPCHK(c, download_sync(c, {{pass_out, d_out, cnt * out_len}, {cls + base, c->s_inf.p, cnt}}));
     } else {
-      rc = tlock_pass(c, pass_us, cnt, pass_out, cls ? cls + base : nullptr, st);
+      rc = tlock_pass(c, pass_us, cnt, pass_out, cls ? cls + base : nullptr, st, mk, pass_in);
       if (rc) return rc;
     }
   }
@@ -99,32 +111,35 @@ static int tlock_passes(blsv_ctx* c, bool host, const uint8_t* us, size_t n, uin
 // in the context's host staging (o points into it) for the caller to copy out: blsv_tlock_open hands
 // nothing over under a rejected sigma. sig_of == nullptr: every item under signature 0.
 int tlock_lat_run(blsv_ctx* c, const uint8_t* sigs96, size_t m, const uint32_t* sig_of, const uint32_t* idle,
-                  size_t n_idle, const uint8_t* us48, size_t n, TlockLatOut& o) {
+                  size_t n_idle, const uint8_t* us48, size_t n, TlockLatOut& o, const uint8_t* cs, size_t mlen) {
   tlock_lat_state& t = c->tlock_lat;
-  const TlockLatLayout l = tlock_lat_layout(m, n, sig_of != nullptr, n_idle);
+  const TlockLatLayout l = tlock_lat_layout(m, n, sig_of != nullptr, n_idle, n * mlen);
   HIPCHK(c, t.buf.ensure(l.total));
   t.up.resize(l.in_total);
   memcpy(t.up.data() + l.o_sigs, sigs96, 96 * m);
   memcpy(t.up.data() + l.o_us, us48, BLSV_U_LEN * n);
   if (sig_of) memcpy(t.up.data() + l.o_sigof, sig_of, 4 * n);
   if (n_idle) memcpy(t.up.data() + l.o_idle, idle, 4 * n_idle);
+  if (mlen) memcpy(t.up.data() + l.o_min, cs, n * mlen);
   uint8_t* d = t.buf.as<uint8_t>();
   HIPCHK(c, h2d(c, d, t.up.data(), l.in_total));
   blsk::launch_lat_tlock(d + l.o_sigs, sig_of ? (const uint32_t*)(d + l.o_sigof) : nullptr, d + l.o_us, n,
                          (const uint32_t*)(d + l.o_idle), n_idle, d + l.o_gt, d + l.o_cls, d + l.o_sigcls, c->stream);
+  // decrypting: the mask kernel behind it over the bytes it wrote, and the download starts behind them
+  if (mlen) blsk::launch_tmask_encoded(d + l.o_gt, d + l.o_cls, BLSV_REJ_OK, n, d + l.o_min, d + l.o_mout, mlen, c->stream);
   HIPCHK(c, hipGetLastError());
   t.down.resize(l.out_total);
-  HIPCHK(c, download_sync(c, {{t.down.data(), d + l.o_gt, l.out_total}}));
-  o.gt = t.down.data();
-  o.cls = o.gt + BLSV_GT_LEN * n;
+  HIPCHK(c, download_sync(c, {{t.down.data(), d + l.o_down, l.out_total}}));
+  o.gt = t.down.data();  // n x 576 bytes, or the n x mlen masked bytes
+  o.cls = t.down.data() + (l.o_cls - l.o_down);
   o.sig_cls = o.cls + n;
   t.launches++;
   t.items += n;
   return BLSV_OK;
 }
 
-void tlock_lat_copy_out(const TlockLatOut& o, size_t n, uint8_t* out_gt576, uint8_t* ok, uint8_t* reject_class) {
-  memcpy(out_gt576, o.gt, BLSV_GT_LEN * n);
+void tlock_lat_copy_out(const TlockLatOut& o, size_t n, uint8_t* out, uint8_t* ok, uint8_t* reject_class, size_t out_len) {
+  memcpy(out, o.gt, out_len * n);
   if (reject_class) memcpy(reject_class, o.cls, n);
   for (size_t i = 0; i < n; i++) ok[i] = o.cls[i] == BLSV_REJ_OK;
 }
@@ -172,6 +187,55 @@ int blsv_tlock_open_dev(blsv_ctx* c, const uint8_t* sig96, const uint8_t* d_us48
   if (rc) return rc;
   if (!n) return BLSV_OK;
   return tlock_passes(c, false, d_us48, n, d_out_gt576, d_reject_class, st);
+}
+
+int blsv_tlock_decrypt(blsv_ctx* c, const uint8_t* sig96, const uint8_t* us48, const uint8_t* cs, size_t mlen, size_t n,
+                       int kdf, uint8_t* out_msgs, uint8_t* ok, uint8_t* reject_class, uint8_t* sig_class) {
+  if (!c) return BLSV_EINVAL;
+  if (!sig96 || (n && (!us48 || !cs || !out_msgs || !ok)) || !tcrypt_fits(kdf, mlen, n))
+    return fail(c, BLSV_EINVAL, "tlock_decrypt: bad arguments");
+  (void)hipSetDevice(c->device);
+  if (tlock_lat_routes(n, 0, std::min(c->tlock_lat.lat_max, c->chunk))) {
+    TlockLatOut o;
+    const int rl = tlock_lat_run(c, sig96, 1, nullptr, nullptr, 0, us48, n, o, cs, mlen);
+    if (rl) return rl;
+    if (sig_class) *sig_class = o.sig_cls[0];
+    if (o.sig_cls[0] != BLSV_REJ_OK)
+      return fail(c, BLSV_EINVAL, "tlock_decrypt: signature rejected (class %d)", (int)o.sig_cls[0]);
+    tlock_lat_copy_out(o, n, out_msgs, ok, reject_class, mlen);
+    return BLSV_OK;
+  }
+  int rc = tlock_prepare_sig(c, sig96, c->stream, sig_class);
+  if (rc) return rc;
+  if (!n) return BLSV_OK;
+  std::vector<uint8_t> own;
+  uint8_t* cls = reject_class;
+  if (!cls) {
+    own.resize(n);
+    cls = own.data();
+  }
+  MaskTail mk;
+  mk.mlen = mlen;
+  mk.host = true;
+  rc = tlock_passes(c, true, us48, n, out_msgs, cls, c->stream, mk, cs);
+  if (rc) return rc;
+  for (size_t i = 0; i < n; i++) ok[i] = cls[i] == BLSV_REJ_OK;
+  return BLSV_OK;
+}
+
+int blsv_tlock_decrypt_dev(blsv_ctx* c, const uint8_t* sig96, const uint8_t* d_us48, const uint8_t* d_cs, size_t mlen,
+                           size_t n, int kdf, uint8_t* d_out_msgs, uint8_t* d_reject_class, void* stream) {
+  if (!c) return BLSV_EINVAL;
+  if (!sig96 || (n && (!d_us48 || !d_cs || !d_out_msgs)) || !tcrypt_fits(kdf, mlen, n))
+    return fail(c, BLSV_EINVAL, "tlock_decrypt_dev: bad arguments");
+  (void)hipSetDevice(c->device);
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  int rc = tlock_prepare_sig(c, sig96, st, nullptr);
+  if (rc) return rc;
+  if (!n) return BLSV_OK;
+  MaskTail mk;
+  mk.mlen = mlen;
+  return tlock_passes(c, false, d_us48, n, d_out_msgs, d_reject_class, st, mk, d_cs);
 }
 
 int blsv_tlock_stats(blsv_ctx* c, uint64_t* prepared, uint64_t* items) {

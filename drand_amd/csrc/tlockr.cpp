@@ -65,9 +65,12 @@ static int rounds_decode(blsv_ctx* c, const uint8_t* sigs96, const std::vector<u
   return BLSV_OK;
 }
 
-// One pass: d_us (cnt x 48 bytes) -> d_out (cnt x 576 bytes), the items' classes in s_inf
+// One pass: d_us (cnt x 48 bytes) -> d_out (cnt x 576 bytes), the items' classes in s_inf. With a mask tail
+// (mk.mlen != 0; blsv_tlock_decrypt_rounds*) the encoding is replaced by the mask kernel over the pass's input
+// bytes mk_in: d_out gets cnt x mlen bytes.
 static int rounds_pass(blsv_ctx* c, const uint8_t* sigs96, const TlockRoundsPass& p, const uint8_t* d_us, uint8_t* d_out,
-                       uint8_t* d_cls_out, uint8_t* d_sig_class, std::vector<uint8_t>& tmp, hipStream_t st) {
+                       uint8_t* d_cls_out, uint8_t* d_sig_class, std::vector<uint8_t>& tmp, hipStream_t st,
+                       const MaskTail& mk, const uint8_t* mk_in) {
   const Staging w = staging(c);
   const RoundsFw fw = rounds_fw(c);
   const size_t cnt = p.cnt, M = p.sig_j.size();
@@ -106,7 +109,12 @@ static int rounds_pass(blsv_ctx* c, const uint8_t* sigs96, const TlockRoundsPass
     // plan in it read too, is the exponentiation's scratch again
     blsk::launch_final_exp(w.F, w.FW, cnt, 0, cnt, w.cls, st, w.LN, w.HQ);
   }
-  blsk::launch_tlock_encode(w.HQ, ucls, cnt, d_out, st);
+  if (mk.mlen) {
+    const int rc = mask_tail(c, mk, ucls, BLSV_REJ_OK, cnt, mk_in, d_out, st);
+    if (rc) return rc;
+  } else {
+    blsk::launch_tlock_encode(w.HQ, ucls, cnt, d_out, st);
+  }
   if (d_cls_out) HIPCHK(c, hipMemcpyAsync(d_cls_out, ucls, cnt, hipMemcpyDeviceToDevice, st));
   HIPCHK(c, hipGetLastError());
   return BLSV_OK;
@@ -116,23 +124,29 @@ static int rounds_pass(blsv_ctx* c, const uint8_t* sigs96, const TlockRoundsPass
 // their classes are wanted). Device buffers (host == false): us, out and cls (optional) are read and
 // written in place on st. Host buffers: a pass's compressed U bytes travel in S, its encoded values come
 // back through F, and each pass ends with the download's synchronisation.
+// With a mask tail, mk_in is the call's n x mlen input bytes and out receives n x mlen bytes; a host call's
+// pass stages both in F (mask_tail).
 static int rounds_passes(blsv_ctx* c, bool host, const uint8_t* sigs96, const uint64_t* counts, size_t m,
-                         const uint8_t* us, size_t n, uint8_t* out, uint8_t* cls, uint8_t* d_sig_class, hipStream_t st) {
+                         const uint8_t* us, size_t n, uint8_t* out, uint8_t* cls, uint8_t* d_sig_class, hipStream_t st,
+                         const MaskTail& mk = MaskTail(), const uint8_t* mk_in = nullptr) {
   int rc = rounds_begin(c, m, n, st);
   if (rc) return rc;
   TlockRoundsCursor cur;
   TlockRoundsPass p;
   std::vector<uint8_t> tmp;
+  const size_t out_len = mk.mlen ? mk.mlen : BLSV_GT_LEN;
   while (open_rounds_next_pass(counts, m, c->cap, c->tlockr.dense_min, cur, p)) {
     const uint8_t* pass_us = us + p.base * BLSV_U_LEN;
-    uint8_t* pass_out = out + p.base * BLSV_GT_LEN;
+    const uint8_t* pass_in = mk.mlen ? mk_in + p.base * mk.mlen : nullptr;
+    uint8_t* pass_out = out + p.base * out_len;
     if (host) {
+      uint8_t* d_out = mask_host_out(c, mk, p.cnt);
       HIPCHK(c, h2d(c, c->S.p, pass_us, p.cnt * BLSV_U_LEN));
-      rc = rounds_pass(c, sigs96, p, c->S.as<uint8_t>(), c->F.as<uint8_t>(), nullptr, d_sig_class, tmp, st);
+      rc = rounds_pass(c, sigs96, p, c->S.as<uint8_t>(), d_out, nullptr, d_sig_class, tmp, st, mk, pass_in);
       if (rc) return rc;
-      HIPCHK(c, download_sync(c, {{pass_out, c->F.p, p.cnt * BLSV_GT_LEN}, {cls + p.base, c->s_inf.p, p.cnt}}));
+      HIPCHK(c, download_sync(c, {{pass_out, d_out, p.cnt * out_len}, {cls + p.base, c->s_inf.p, p.cnt}}));
     } else {
-      rc = rounds_pass(c, sigs96, p, pass_us, pass_out, cls ? cls + p.base : nullptr, d_sig_class, tmp, st);
+      rc = rounds_pass(c, sigs96, p, pass_us, pass_out, cls ? cls + p.base : nullptr, d_sig_class, tmp, st, mk, pass_in);
       if (rc) return rc;
     }
   }
@@ -197,6 +211,59 @@ int blsv_tlock_open_rounds_dev(blsv_ctx* c, const uint8_t* sigs96, const uint64_
   (void)hipSetDevice(c->device);
   hipStream_t st = stream ? (hipStream_t)stream : c->stream;
   return rounds_passes(c, false, sigs96, counts, m, d_us48, n, d_out_gt576, d_reject_class, d_sig_class, st);
+}
+
+int blsv_tlock_decrypt_rounds(blsv_ctx* c, const uint8_t* sigs96, const uint64_t* counts, size_t m, const uint8_t* us48,
+                              const uint8_t* cs, size_t mlen, size_t n, int kdf, uint8_t* out_msgs, uint8_t* ok,
+                              uint8_t* reject_class, uint8_t* sig_class) {
+  if (!c) return BLSV_EINVAL;
+  if ((m && (!sigs96 || !counts)) || (n && (!us48 || !cs || !out_msgs || !ok)) || !tcrypt_fits(kdf, mlen, n) ||
+      !open_rounds_fits(counts, m, n))
+    return fail(c, BLSV_EINVAL, "tlock_decrypt_rounds: bad arguments");
+  (void)hipSetDevice(c->device);
+  const size_t lat_max = std::min(c->tlock_lat.lat_max, c->chunk);
+  if (tlock_lat_routes(n, 0, lat_max) && tlock_lat_plan(counts, m, lat_max, c->tlock_lat.plan)) {
+    const TlockLatPlan& p = c->tlock_lat.plan;
+    TlockLatOut o;
+    const int rl = tlock_lat_run(c, sigs96, m, p.sig_of.data(), p.idle.data(), p.idle.size(), us48, n, o, cs, mlen);
+    if (rl) return rl;
+    if (sig_class) memcpy(sig_class, o.sig_cls, m);
+    tlock_lat_copy_out(o, n, out_msgs, ok, reject_class, mlen);
+    return BLSV_OK;
+  }
+  uint8_t* d_sc = nullptr;
+  if (sig_class && m) {
+    HIPCHK(c, c->misc.ensure(m));
+    d_sc = c->misc.as<uint8_t>();
+  }
+  std::vector<uint8_t> own;
+  uint8_t* cls = reject_class;
+  if (!cls && n) {
+    own.resize(n);
+    cls = own.data();
+  }
+  MaskTail mk;
+  mk.mlen = mlen;
+  mk.host = true;
+  int rc = rounds_passes(c, true, sigs96, counts, m, us48, n, out_msgs, cls, d_sc, c->stream, mk, cs);
+  if (rc) return rc;
+  if (d_sc) HIPCHK(c, download_sync(c, {{sig_class, d_sc, m}}));
+  for (size_t i = 0; i < n; i++) ok[i] = cls[i] == BLSV_REJ_OK;
+  return BLSV_OK;
+}
+
+int blsv_tlock_decrypt_rounds_dev(blsv_ctx* c, const uint8_t* sigs96, const uint64_t* counts, size_t m,
+                                  const uint8_t* d_us48, const uint8_t* d_cs, size_t mlen, size_t n, int kdf,
+                                  uint8_t* d_out_msgs, uint8_t* d_reject_class, uint8_t* d_sig_class, void* stream) {
+  if (!c) return BLSV_EINVAL;
+  if ((m && (!sigs96 || !counts)) || (n && (!d_us48 || !d_cs || !d_out_msgs)) || !tcrypt_fits(kdf, mlen, n) ||
+      !open_rounds_fits(counts, m, n))
+    return fail(c, BLSV_EINVAL, "tlock_decrypt_rounds_dev: bad arguments");
+  (void)hipSetDevice(c->device);
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  MaskTail mk;
+  mk.mlen = mlen;
+  return rounds_passes(c, false, sigs96, counts, m, d_us48, n, d_out_msgs, d_reject_class, d_sig_class, st, mk, d_cs);
 }
 
 int blsv_tlock_open_rounds_stats(blsv_ctx* c, uint64_t* prepared, uint64_t* items) {

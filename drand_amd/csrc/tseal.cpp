@@ -62,9 +62,11 @@ static int seal_prepare(blsv_ctx* c, const uint8_t* pk48, uint64_t round, size_t
   return BLSV_OK;
 }
 
-// One pass of cnt <= cap items: d_scalars (cnt x 32 bytes) -> d_us (cnt x 48), d_gt (cnt x 576), d_ok (cnt)
+// One pass of cnt <= cap items: d_scalars (cnt x 32 bytes) -> d_us (cnt x 48), d_gt (cnt x 576), d_ok (cnt). With
+// a mask tail (mk.mlen != 0; blsv_tlock_encrypt*) the encoding is replaced by the mask kernel over the pass's
+// message bytes mk_in: d_gt gets cnt x mlen ciphertext bytes.
 static int seal_pass(blsv_ctx* c, const uint8_t* d_scalars, size_t cnt, uint8_t* d_us, uint8_t* d_gt, uint8_t* d_ok,
-                     hipStream_t st) {
+                     hipStream_t st, const MaskTail& mk, const uint8_t* mk_in) {
   const tseal_state& t = c->tseal;
   const Staging w = staging(c);
   uint8_t* cls = w.s_inf;
@@ -73,7 +75,12 @@ static int seal_pass(blsv_ctx* c, const uint8_t* d_scalars, size_t cnt, uint8_t*
     blsk::launch_tseal_u(t.t1.as<uint32_t>(), d_scalars, cnt, d_us, d_ok, cls, st);
     blsk::launch_tseal_gt(t.t2.as<uint32_t>(), d_scalars, cls, cnt, w.HQ, st);
   }
-  blsk::launch_tlock_encode(w.HQ, cls, cnt, d_gt, st);
+  if (mk.mlen) {
+    const int rc = mask_tail(c, mk, cls, BLSV_REJ_OK, cnt, mk_in, d_gt, st);
+    if (rc) return rc;
+  } else {
+    blsk::launch_tlock_encode(w.HQ, cls, cnt, d_gt, st);
+  }
   HIPCHK(c, hipGetLastError());
   return BLSV_OK;
 }
@@ -81,26 +88,36 @@ static int seal_pass(blsv_ctx* c, const uint8_t* d_scalars, size_t cnt, uint8_t*
 // Every pass of n items under the prepared base. Device buffers (host == false): read and written in
 // place on st. Host buffers: a pass's scalars travel in S and are cleared there behind the kernels that
 // read them, its U bytes come back through H, its ok bytes through h_inf and its encoded values through
-// F, and each pass ends with the download's synchronisation.
+// F, and each pass ends with the download's synchronisation. With a mask tail, mk_in is the call's n x mlen
+// message bytes and gt receives n x mlen ciphertext bytes; a host call's pass stages both in F (mask_tail),
+// and the captured K (with a host call's staged plaintexts) is cleared behind the kernel, also when the
+// pass failed.
 static int seal_passes(blsv_ctx* c, bool host, const uint8_t* scalars, size_t n, uint8_t* us, uint8_t* gt, uint8_t* ok,
-                       hipStream_t st) {
+                       hipStream_t st, const MaskTail& mk = MaskTail(), const uint8_t* mk_in = nullptr) {
   int rc = ensure_workspace(c, n);
   if (rc) return rc;
+  const size_t out_len = mk.mlen ? mk.mlen : BLSV_GT_LEN;
   for (size_t base = 0; base < n; base += c->cap) {
     const size_t cnt = std::min(c->cap, n - base);
+    const uint8_t* pass_in = mk.mlen ? mk_in + base * mk.mlen : nullptr;
     if (host) {
+      uint8_t* d_out = mask_host_out(c, mk, cnt);
       HIPCHK(c, hipMemcpyAsync(c->S.p, scalars + base * BLSV_SCALAR_LEN, cnt * BLSV_SCALAR_LEN, hipMemcpyHostToDevice, st));
-      rc = seal_pass(c, c->S.as<uint8_t>(), cnt, c->H.as<uint8_t>(), c->F.as<uint8_t>(), c->h_inf.as<uint8_t>(), st);
-      const hipError_t wipe = hipMemsetAsync(c->S.p, 0, cnt * BLSV_SCALAR_LEN, st);  // also when the pass failed
+      rc = seal_pass(c, c->S.as<uint8_t>(), cnt, c->H.as<uint8_t>(), d_out, c->h_inf.as<uint8_t>(), st, mk, pass_in);
+      hipError_t wipe = hipMemsetAsync(c->S.p, 0, cnt * BLSV_SCALAR_LEN, st);  // also when the pass failed
+      const hipError_t wipe_k = mask_wipe(c, mk, cnt, st);
+      if (wipe == hipSuccess) wipe = wipe_k;
       if (rc) return rc;
       HIPCHK(c, wipe);
       HIPCHK(c, download_sync(c, {{us + base * BLSV_U_LEN, c->H.p, cnt * BLSV_U_LEN},
-                                  {gt + base * BLSV_GT_LEN, c->F.p, cnt * BLSV_GT_LEN},
+                                  {gt + base * out_len, d_out, cnt * out_len},
                                   {ok + base, c->h_inf.p, cnt}}));
     } else {
-      rc = seal_pass(c, scalars + base * BLSV_SCALAR_LEN, cnt, us + base * BLSV_U_LEN, gt + base * BLSV_GT_LEN,
-                     ok + base, st);
+      rc = seal_pass(c, scalars + base * BLSV_SCALAR_LEN, cnt, us + base * BLSV_U_LEN, gt + base * out_len, ok + base,
+                     st, mk, pass_in);
+      const hipError_t wipe_k = mask_wipe(c, mk, cnt, st);
       if (rc) return rc;
+      HIPCHK(c, wipe_k);
     }
   }
   c->tseal.items += n;
@@ -150,6 +167,46 @@ int blsv_tlock_seal_dev(blsv_ctx* c, const uint8_t* pk48, uint64_t round, const 
   if (rc) return rc;
   if (!n) return BLSV_OK;
   return seal_passes(c, false, d_scalars32, n, d_out_us48, d_out_gt576, d_ok, st);
+}
+
+int blsv_tlock_encrypt(blsv_ctx* c, const uint8_t* pk48, uint64_t round, const uint8_t* scalars32, const uint8_t* msgs,
+                       size_t mlen, size_t n, int kdf, uint8_t* out_us48, uint8_t* out_cs, uint8_t* ok) {
+  if (!c) return BLSV_EINVAL;
+  if ((n && (!scalars32 || !msgs || !out_us48 || !out_cs || !ok)) || !tcrypt_fits(kdf, mlen, n))
+    return fail(c, BLSV_EINVAL, "tlock_encrypt: bad arguments");
+  (void)hipSetDevice(c->device);
+  const uint8_t* key;
+  int rc = seal_key(c, pk48, &key);
+  if (rc) return rc;
+  if (tseal_lat_routes(n, std::min(c->tseal_lat.lat_max, c->chunk)))
+    return tseal_lat_run(c, key, nullptr, round, scalars32, n, out_us48, out_cs, ok, msgs, mlen);
+  rc = seal_prepare(c, key, round, n, c->stream);
+  if (rc) return rc;
+  if (!n) return BLSV_OK;
+  MaskTail mk;
+  mk.mlen = mlen;
+  mk.host = mk.secret = true;
+  return seal_passes(c, true, scalars32, n, out_us48, out_cs, ok, c->stream, mk, msgs);
+}
+
+int blsv_tlock_encrypt_dev(blsv_ctx* c, const uint8_t* pk48, uint64_t round, const uint8_t* d_scalars32,
+                           const uint8_t* d_msgs, size_t mlen, size_t n, int kdf, uint8_t* d_out_us48, uint8_t* d_out_cs,
+                           uint8_t* d_ok, void* stream) {
+  if (!c) return BLSV_EINVAL;
+  if ((n && (!d_scalars32 || !d_msgs || !d_out_us48 || !d_out_cs || !d_ok)) || !tcrypt_fits(kdf, mlen, n))
+    return fail(c, BLSV_EINVAL, "tlock_encrypt_dev: bad arguments");
+  (void)hipSetDevice(c->device);
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  const uint8_t* key;
+  int rc = seal_key(c, pk48, &key);
+  if (rc) return rc;
+  rc = seal_prepare(c, key, round, n, st);
+  if (rc) return rc;
+  if (!n) return BLSV_OK;
+  MaskTail mk;
+  mk.mlen = mlen;
+  mk.secret = true;
+  return seal_passes(c, false, d_scalars32, n, d_out_us48, d_out_cs, d_ok, st, mk, d_msgs);
 }
 
 int blsv_tlock_seal_stats(blsv_ctx* c, uint64_t* bases, uint64_t* items) {

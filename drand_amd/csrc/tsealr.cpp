@@ -46,9 +46,11 @@ int sealr_prepare(blsv_ctx* c, const uint8_t* pk48, size_t n, hipStream_t st) {
 }
 
 // One pass of cnt <= cap items: d_rounds (cnt), d_scalars (cnt x 32 bytes) -> d_us (cnt x 48), d_gt
-// (cnt x 576), d_ok (cnt). The points P_i wait in S (seal_rounds_layout) for the lines pass.
+// (cnt x 576), d_ok (cnt). The points P_i wait in S (seal_rounds_layout) for the lines pass. With a mask tail
+// (mk.mlen != 0; blsv_tlock_encrypt_rounds*) the encoding is replaced by the mask kernel over the pass's message
+// bytes mk_in: d_gt gets cnt x mlen ciphertext bytes.
 static int sealr_pass(blsv_ctx* c, const uint64_t* d_rounds, const uint8_t* d_scalars, size_t cnt, uint8_t* d_us,
-                      uint8_t* d_gt, uint8_t* d_ok, hipStream_t st) {
+                      uint8_t* d_gt, uint8_t* d_ok, hipStream_t st, const MaskTail& mk, const uint8_t* mk_in) {
   const Staging w = staging(c);
   uint32_t* P = w.S + seal_rounds_layout(cnt).o_p / 4;
   uint8_t* cls = w.s_inf;
@@ -74,7 +76,12 @@ static int sealr_pass(blsv_ctx* c, const uint64_t* d_rounds, const uint8_t* d_sc
     // the lines are read: the park goes to LN and the values are captured in HQ, as in an opening
     blsk::launch_final_exp(w.F, w.FW, cnt, 0, cnt, w.cls, st, w.LN, w.HQ);
   }
-  blsk::launch_tlock_encode(w.HQ, cls, cnt, d_gt, st);
+  if (mk.mlen) {
+    const int rc = mask_tail(c, mk, cls, BLSV_REJ_OK, cnt, mk_in, d_gt, st);
+    if (rc) return rc;
+  } else {
+    blsk::launch_tlock_encode(w.HQ, cls, cnt, d_gt, st);
+  }
   HIPCHK(c, hipGetLastError());
   return BLSV_OK;
 }
@@ -83,32 +90,40 @@ static int sealr_pass(blsv_ctx* c, const uint64_t* d_rounds, const uint8_t* d_sc
 // on st. Host buffers: a pass's scalars and rounds travel in S behind the P table, its U and ok bytes come
 // back from there and its encoded values through F, and each pass ends with the download's
 // synchronisation. Either way the P table -- and a host call's scalars with it -- is cleared behind the
-// kernels that read it, also when the pass failed.
+// kernels that read it, also when the pass failed. With a mask tail, mk_in is the call's n x mlen message bytes
+// and gt receives n x mlen ciphertext bytes; a host call's pass stages both in F (mask_tail), and the captured
+// K (with a host call's staged plaintexts) is cleared with the P table.
 static int sealr_passes(blsv_ctx* c, bool host, const uint64_t* rounds, const uint8_t* scalars, size_t n, uint8_t* us,
-                        uint8_t* gt, uint8_t* ok, hipStream_t st) {
+                        uint8_t* gt, uint8_t* ok, hipStream_t st, const MaskTail& mk = MaskTail(),
+                        const uint8_t* mk_in = nullptr) {
   int rc = ensure_workspace(c, n);
   if (rc) return rc;
+  const size_t out_len = mk.mlen ? mk.mlen : BLSV_GT_LEN;
   for (size_t base = 0; base < n; base += c->cap) {
     const size_t cnt = std::min(c->cap, n - base);
     const SealRoundsLayout l = seal_rounds_layout(cnt);
+    const uint8_t* pass_in = mk.mlen ? mk_in + base * mk.mlen : nullptr;
+    uint8_t* d_out = mask_host_out(c, mk, cnt);  // a host call's
     uint8_t* S = c->S.as<uint8_t>();
     if (host) {
       hipError_t up = hipMemcpyAsync(S + l.o_scalars, scalars + base * BLSV_SCALAR_LEN, cnt * BLSV_SCALAR_LEN,
                                      hipMemcpyHostToDevice, st);
       if (up == hipSuccess) up = hipMemcpyAsync(S + l.o_rounds, rounds + base, cnt * 8, hipMemcpyHostToDevice, st);
       rc = up != hipSuccess ? fail(c, BLSV_EHIP, "tlock_seal_rounds: upload: %s", hipGetErrorString(up))
-                            : sealr_pass(c, (const uint64_t*)(S + l.o_rounds), S + l.o_scalars, cnt, S + l.o_us,
-                                         c->F.as<uint8_t>(), S + l.o_ok, st);
+                            : sealr_pass(c, (const uint64_t*)(S + l.o_rounds), S + l.o_scalars, cnt, S + l.o_us, d_out,
+                                         S + l.o_ok, st, mk, pass_in);
     } else {
       rc = sealr_pass(c, rounds + base, scalars + base * BLSV_SCALAR_LEN, cnt, us + base * BLSV_U_LEN,
-                      gt + base * BLSV_GT_LEN, ok + base, st);
+                      gt + base * out_len, ok + base, st, mk, pass_in);
     }
-    const hipError_t wipe = hipMemsetAsync(S, 0, host ? l.secret : l.o_scalars, st);
+    hipError_t wipe = hipMemsetAsync(S, 0, host ? l.secret : l.o_scalars, st);
+    const hipError_t wipe_k = mask_wipe(c, mk, cnt, st);
+    if (wipe == hipSuccess) wipe = wipe_k;
     if (rc) return rc;
     HIPCHK(c, wipe);
     if (host)
       HIPCHK(c, download_sync(c, {{us + base * BLSV_U_LEN, S + l.o_us, cnt * BLSV_U_LEN},
-                                  {gt + base * BLSV_GT_LEN, c->F.p, cnt * BLSV_GT_LEN},
+                                  {gt + base * out_len, d_out, cnt * out_len},
                                   {ok + base, S + l.o_ok, cnt}}));
   }
   c->tsealr.items += n;
@@ -149,6 +164,49 @@ int blsv_tlock_seal_rounds_dev(blsv_ctx* c, const uint8_t* pk48, const uint64_t*
   if (rc) return rc;
   if (!n) return BLSV_OK;
   return sealr_passes(c, false, d_rounds, d_scalars32, n, d_out_us48, d_out_gt576, d_ok, st);
+}
+
+int blsv_tlock_encrypt_rounds(blsv_ctx* c, const uint8_t* pk48, const uint64_t* rounds, const uint8_t* scalars32,
+                              const uint8_t* msgs, size_t mlen, size_t n, int kdf, uint8_t* out_us48, uint8_t* out_cs,
+                              uint8_t* ok) {
+  if (!c) return BLSV_EINVAL;
+  if ((n && (!rounds || !scalars32 || !msgs || !out_us48 || !out_cs || !ok)) || !tcrypt_fits(kdf, mlen, n) ||
+      !seal_rounds_fits(n))
+    return fail(c, BLSV_EINVAL, "tlock_encrypt_rounds: bad arguments");
+  (void)hipSetDevice(c->device);
+  const uint8_t* key;
+  int rc = seal_key(c, pk48, &key);
+  if (rc) return rc;
+  if (tseal_lat_routes(n, std::min(c->tseal_lat.lat_max, c->chunk)))
+    return tseal_lat_run(c, key, rounds, 0, scalars32, n, out_us48, out_cs, ok, msgs, mlen);
+  rc = sealr_prepare(c, key, n, c->stream);
+  if (rc) return rc;
+  if (!n) return BLSV_OK;
+  MaskTail mk;
+  mk.mlen = mlen;
+  mk.host = mk.secret = true;
+  return sealr_passes(c, true, rounds, scalars32, n, out_us48, out_cs, ok, c->stream, mk, msgs);
+}
+
+int blsv_tlock_encrypt_rounds_dev(blsv_ctx* c, const uint8_t* pk48, const uint64_t* d_rounds, const uint8_t* d_scalars32,
+                                  const uint8_t* d_msgs, size_t mlen, size_t n, int kdf, uint8_t* d_out_us48,
+                                  uint8_t* d_out_cs, uint8_t* d_ok, void* stream) {
+  if (!c) return BLSV_EINVAL;
+  if ((n && (!d_rounds || !d_scalars32 || !d_msgs || !d_out_us48 || !d_out_cs || !d_ok)) || ((uintptr_t)d_rounds & 7) ||
+      !tcrypt_fits(kdf, mlen, n) || !seal_rounds_fits(n))
+    return fail(c, BLSV_EINVAL, "tlock_encrypt_rounds_dev: bad arguments");
+  (void)hipSetDevice(c->device);
+  hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+  const uint8_t* key;
+  int rc = seal_key(c, pk48, &key);
+  if (rc) return rc;
+  rc = sealr_prepare(c, key, n, st);
+  if (rc) return rc;
+  if (!n) return BLSV_OK;
+  MaskTail mk;
+  mk.mlen = mlen;
+  mk.secret = true;
+  return sealr_passes(c, false, d_rounds, d_scalars32, n, d_out_us48, d_out_cs, d_ok, st, mk, d_msgs);
 }
 
 int blsv_tlock_seal_rounds_stats(blsv_ctx* c, uint64_t* keys, uint64_t* items) {

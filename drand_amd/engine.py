@@ -77,6 +77,45 @@ class TsealResult:
     gt: list
 
 
+@dataclass
+class TdecryptResult:
+    """Outcome of Engine.tlock_decrypt: ok[i] (U_i decoded), reject classes (REJ_*), msgs[i] = the item's mlen
+    bytes cs[i] XOR kdf(e(U_i, sigma)^3), or None for a rejected item."""
+    ok: list
+    reject_class: list
+    msgs: list
+
+
+@dataclass
+class TdecryptRoundsResult:
+    """Outcome of Engine.tlock_decrypt_rounds: ok, reject_class and msgs per item in packed order (as
+    TdecryptResult's), sig_class[j] per round signature (0 = decoded)."""
+    ok: list
+    reject_class: list
+    msgs: list
+    sig_class: list
+
+
+@dataclass
+class TencryptResult:
+    """Outcome of Engine.tlock_encrypt: ok[i] (sealed), us[i] = compress(k_i G1), cs[i] = msgs[i] XOR kdf(K_i);
+    us[i] and cs[i] are None for a refused scalar (k_i == 0 mod r). K_i itself never leaves the device."""
+    ok: list
+    us: list
+    cs: list
+
+
+def _packed(items, what):
+    """Messages of one length 1 .. TLOCK_MSG_MAX, packed: (bytes, mlen)."""
+    items = [bytes(x) for x in items]
+    mlen = len(items[0]) if items else 1
+    if any(len(x) != mlen for x in items):
+        raise ValueError("%s of one call have one length (callers.timelock_* pads ragged ones)" % what)
+    if not 1 <= mlen <= _lib.TLOCK_MSG_MAX:
+        raise ValueError("%s are 1 .. %d bytes" % (what, _lib.TLOCK_MSG_MAX))
+    return b"".join(items), mlen
+
+
 def _scalar32(k):
     """A sealing scalar as 32 bytes big-endian: an int in [0, 2^256) or 32 bytes already."""
     if isinstance(k, (bytes, bytearray, memoryview)):
@@ -599,6 +638,131 @@ class Engine:
         a, b = ctypes.c_uint64(), ctypes.c_uint64()
         self._check(self.lib.blsv_tlock_seal_rounds_stats(self._h, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value
+
+    # ------------------------------------------------------------------ timelock in one call
+    # include/blsverify.h "timelock in one call": the four passes above with the key stream (KDF_SHA256_CTR,
+    # callers.kdf_sha256_ctr) and the XOR fused on the device; mlen bytes per item cross to the host, not 576.
+    def tlock_decrypt(self, sig, us, cs, kdf=_lib.KDF_SHA256_CTR):
+        """blsv_tlock_decrypt: TdecryptResult(ok, reject_class, msgs) over the ciphertexts (us[i], cs[i]) under
+        the 96-byte round signature `sig`; every cs[i] has the same length, 1 .. 256 bytes. msgs[i] equals
+        cs[i] XOR kdf_sha256_ctr(tlock_open(sig, us).gt[i]), or None where U_i did not decode. Raises
+        SignatureRejected as tlock_open does. The signature is NOT verified here."""
+        sig = bytes(sig)
+        us = [bytes(u) for u in us]
+        if len(sig) != 96:
+            raise ValueError("the round signature is 96 bytes")
+        if any(len(u) != 48 for u in us):
+            raise ValueError("U values must be 48 bytes (reject wrong lengths host-side)")
+        n = len(us)
+        cb, mlen = _packed(cs, "ciphertexts")
+        if len(cb) != n * mlen:
+            raise ValueError("one ciphertext per U value")
+        out, ok, cls = _lib.out_buf(n * mlen), _lib.out_buf(n), _lib.out_buf(n)
+        sc = ctypes.c_uint8()
+        rc = self.lib.blsv_tlock_decrypt(self._h, _lib.buf(sig), _lib.buf(b"".join(us)), _lib.buf(cb), mlen, n, int(kdf),
+                                         out, ok, cls, ctypes.cast(ctypes.byref(sc), u8p))
+        if rc == _lib.BLSV_EINVAL and sc.value:
+            raise SignatureRejected(rc, self.lib.blsv_last_error(self._h).decode(), sc.value)
+        self._check(rc)
+        ob = bytes(out)
+        oks = [bool(x) for x in list(ok)[:n]]
+        return TdecryptResult(oks, list(cls)[:n], [ob[mlen * i:mlen * i + mlen] if oks[i] else None for i in range(n)])
+
+    def tlock_decrypt_dev(self, sig, d_us, d_cs, mlen, n, d_out, d_cls=None, stream=None, kdf=_lib.KDF_SHA256_CTR):
+        """blsv_tlock_decrypt_dev: n device-resident U values (48 bytes each) and ciphertexts (mlen bytes each,
+        any alignment) -> n x mlen bytes at d_out (d_out == d_cs is allowed), optional class bytes at d_cls;
+        asynchronous on `stream` except for the read-back of a new signature's decode class."""
+        sig = bytes(sig)
+        if len(sig) != 96:
+            raise ValueError("the round signature is 96 bytes")
+        self._check(self.lib.blsv_tlock_decrypt_dev(self._h, _lib.buf(sig), d_us, d_cs, int(mlen), n, int(kdf), d_out,
+                                                    d_cls, stream))
+
+    def tlock_decrypt_rounds(self, sigs, us_per_round, cs_per_round, kdf=_lib.KDF_SHA256_CTR):
+        """blsv_tlock_decrypt_rounds: as tlock_open_rounds takes `sigs` and `us_per_round`, with round j's
+        ciphertext bodies in cs_per_round[j] (one length for the whole call). Returns
+        TdecryptRoundsResult(ok, reject_class, msgs, sig_class) in packed order; msgs[i] is None where the
+        item did not open. The signatures are NOT verified here."""
+        runs = [[bytes(u) for u in run] for run in us_per_round]
+        us = [u for run in runs for u in run]
+        if any(len(u) != 48 for u in us):
+            raise ValueError("U values must be 48 bytes (reject wrong lengths host-side)")
+        cruns = [list(run) for run in cs_per_round]
+        if [len(r) for r in cruns] != [len(r) for r in runs]:
+            raise ValueError("one ciphertext per U value, round by round")
+        sb, counts, m = self._rounds_args(sigs, [len(run) for run in runs])
+        n = len(us)
+        cb, mlen = _packed([c for run in cruns for c in run], "ciphertexts")
+        out, ok, cls, sc = _lib.out_buf(n * mlen), _lib.out_buf(n), _lib.out_buf(n), _lib.out_buf(m)
+        self._check(self.lib.blsv_tlock_decrypt_rounds(self._h, sb, counts, m, _lib.buf(b"".join(us)), _lib.buf(cb), mlen,
+                                                       n, int(kdf), out, ok, cls, sc))
+        ob = bytes(out)
+        oks = [bool(x) for x in list(ok)[:n]]
+        return TdecryptRoundsResult(oks, list(cls)[:n],
+                                    [ob[mlen * i:mlen * i + mlen] if oks[i] else None for i in range(n)], list(sc)[:m])
+
+    def tlock_decrypt_rounds_dev(self, sigs, counts, d_us, d_cs, mlen, n, d_out, d_cls=None, d_sig_cls=None, stream=None,
+                                 kdf=_lib.KDF_SHA256_CTR):
+        """blsv_tlock_decrypt_rounds_dev: `sigs` and `counts` on the host over n device-resident U values and
+        ciphertexts (mlen bytes each, any alignment) -> n x mlen bytes at d_out, optional class bytes at d_cls
+        (n) and d_sig_cls (m); asynchronous on `stream`, no class is read back."""
+        sb, cn, m = self._rounds_args(sigs, counts)
+        self._check(self.lib.blsv_tlock_decrypt_rounds_dev(self._h, sb, cn, m, d_us, d_cs, int(mlen), n, int(kdf), d_out,
+                                                           d_cls, d_sig_cls, stream))
+
+    def _encrypt_result(self, n, mlen, us, cs, ok):
+        ub, cb = bytes(us), bytes(cs)
+        oks = [bool(x) for x in list(ok)[:n]]
+        return TencryptResult(oks, [ub[48 * i:48 * i + 48] if oks[i] else None for i in range(n)],
+                              [cb[mlen * i:mlen * i + mlen] if oks[i] else None for i in range(n)])
+
+    def tlock_encrypt(self, round_, scalars, msgs, pk48=None, kdf=_lib.KDF_SHA256_CTR):
+        """blsv_tlock_encrypt: TencryptResult(ok, us, cs), message i (one length per call, 1 .. 256 bytes)
+        locked to `round_` with scalars[i] (as tlock_seal takes them) under pk48 (None = the group key):
+        cs[i] = msgs[i] XOR kdf_sha256_ctr(K_i) with K_i what tlock_seal returns as gt[i]. A scalar == 0
+        (mod r) is refused: ok False, us and cs None."""
+        sc = [_scalar32(k) for k in scalars]
+        n = len(sc)
+        mb, mlen = _packed(msgs, "messages")
+        if len(mb) != n * mlen:
+            raise ValueError("one message per scalar")
+        us, cs, ok = _lib.out_buf(n * 48), _lib.out_buf(n * mlen), _lib.out_buf(n)
+        self._check(self.lib.blsv_tlock_encrypt(self._h, self._seal_key(pk48), int(round_), _lib.buf(b"".join(sc)),
+                                                _lib.buf(mb), mlen, n, int(kdf), us, cs, ok))
+        return self._encrypt_result(n, mlen, us, cs, ok)
+
+    def tlock_encrypt_dev(self, round_, d_scalars, d_msgs, mlen, n, d_us, d_cs, d_ok, pk48=None, stream=None,
+                          kdf=_lib.KDF_SHA256_CTR):
+        """blsv_tlock_encrypt_dev: n device-resident scalars (32 bytes each) and messages (mlen bytes each, any
+        alignment) -> n x 48 bytes at d_us, n x mlen bytes at d_cs (d_cs == d_msgs is allowed) and n ok bytes
+        at d_ok; asynchronous on `stream` except for the build of a (key, round) that is not the cached one."""
+        self._check(self.lib.blsv_tlock_encrypt_dev(self._h, self._seal_key(pk48), int(round_), d_scalars, d_msgs,
+                                                    int(mlen), n, int(kdf), d_us, d_cs, d_ok, stream))
+
+    def tlock_encrypt_rounds(self, rounds, scalars, msgs, pk48=None, kdf=_lib.KDF_SHA256_CTR):
+        """blsv_tlock_encrypt_rounds: TencryptResult(ok, us, cs), message i locked to rounds[i] (any uint64) with
+        scalars[i]; the outputs are those of tlock_encrypt(rounds[i], [scalars[i]], [msgs[i]])."""
+        rounds = [int(r) for r in rounds]
+        sc = [_scalar32(k) for k in scalars]
+        n = len(sc)
+        if len(rounds) != n:
+            raise ValueError("%d rounds for %d scalars" % (len(rounds), n))
+        if any(not 0 <= r < 1 << 64 for r in rounds):
+            raise ValueError("a round is a uint64")
+        mb, mlen = _packed(msgs, "messages")
+        if len(mb) != n * mlen:
+            raise ValueError("one message per scalar")
+        us, cs, ok = _lib.out_buf(n * 48), _lib.out_buf(n * mlen), _lib.out_buf(n)
+        self._check(self.lib.blsv_tlock_encrypt_rounds(self._h, self._seal_key(pk48), (ctypes.c_uint64 * max(n, 1))(*rounds),
+                                                       _lib.buf(b"".join(sc)), _lib.buf(mb), mlen, n, int(kdf), us, cs, ok))
+        return self._encrypt_result(n, mlen, us, cs, ok)
+
+    def tlock_encrypt_rounds_dev(self, d_rounds, d_scalars, d_msgs, mlen, n, d_us, d_cs, d_ok, pk48=None, stream=None,
+                                 kdf=_lib.KDF_SHA256_CTR):
+        """blsv_tlock_encrypt_rounds_dev: n device-resident rounds (uint64 each, 8-byte aligned), scalars and
+        messages (mlen bytes each, any alignment) -> d_us, d_cs and d_ok as tlock_encrypt_dev writes them."""
+        self._check(self.lib.blsv_tlock_encrypt_rounds_dev(self._h, self._seal_key(pk48), d_rounds, d_scalars, d_msgs,
+                                                           int(mlen), n, int(kdf), d_us, d_cs, d_ok, stream))
 
     # ------------------------------------------------------------------ stage profiling
     STAGES = ("hash", "decompress", "miller", "final_exp", "finish", "lat", "rlc", "tlock")

@@ -373,7 +373,8 @@ int blsv_rlc_stats(blsv_ctx* ctx, uint64_t* groups, uint64_t* groups_failed, uin
  * PARITY UNPINNED, two items: the exponent lambda (the cube) and the coefficient order above are kilic
  * GT marshalling as recalled; the reference holds no Gt fixture (its timelock test only round-trips
  * random data), so neither is pinned against it. Both are pinned against this repository's own oracle.
- * The KDF that turns E_i into a key stream is the caller's (kyber's is BLAKE2Xs over GT.MarshalBinary).
+ * The KDF that turns E_i into a key stream is the caller's (kyber's is BLAKE2Xs over GT.MarshalBinary); or see
+ * "Timelock in one call" below, which runs this project's own KDF and the XOR on the device.
  *
  * Prepared-signature cache: the context keeps the prepared form of the LAST sigma (its 96 bytes and
  * the table of its 68 Miller lines' P-independent coefficients, 19,584 bytes on the device). A call with
@@ -647,6 +648,88 @@ int blsv_tlock_seal_rounds_stats(blsv_ctx* ctx, uint64_t* keys, uint64_t* items)
  */
 size_t blsv_set_tseal_lat_max(blsv_ctx* ctx, size_t items); /* returns the previous value */
 int blsv_tseal_lat_stats(blsv_ctx* ctx, uint64_t* launches, uint64_t* items);
+
+/*
+ * Timelock in one call: the entry points above hand the Gt value back raw and leave the key stream and the
+ * XOR to the caller. The eight below are the same passes with that tail fused on the device: one lane per
+ * item hashes the value it has just computed and masks the item's message bytes, so what crosses to the
+ * host is mlen bytes per item, not BLSV_GT_LEN, and on the sealing side K_i never leaves the device.
+ *
+ * KDF. kdf selects the key stream. BLSV_KDF_SHA256_CTR is the only one:
+ *     stream(G, mlen) = SHA-256(G || BE32(0)) || SHA-256(G || BE32(1)) || ...   truncated to mlen bytes
+ * with G the BLSV_GT_LEN-byte encoding defined under blsv_tlock_open. THIS KDF IS THE PROJECT'S OWN. kyber's
+ * timelock uses BLAKE2Xs over GT.MarshalBinary, which nothing here can pin; a ciphertext produced by kyber
+ * does not open under BLSV_KDF_SHA256_CTR, nor the other way round. The argument exists so that kyber's can
+ * be added beside it. Any other kdf value returns BLSV_EINVAL with no output touched.
+ *
+ * Messages. mlen is uniform per call, 1 .. BLSV_TLOCK_MSG_MAX bytes; messages and ciphertexts are packed
+ * n x mlen bytes with no padding and NO alignment requirement, on the host and on the device. mlen = 0,
+ * mlen > BLSV_TLOCK_MSG_MAX, or a byte count that overflows size_t is BLSV_EINVAL with no output touched.
+ * Only the bytes [i mlen, (i + 1) mlen) of item i are written. In place is allowed: out_msgs == cs and
+ * out_cs == msgs (each lane reads its bytes before it writes them); any other overlap is not.
+ *
+ * Contract. For every item, out_msgs[i] = cs[i] XOR stream(G_i, mlen) where G_i is the BLSV_GT_LEN bytes the
+ * matching entry point -- blsv_tlock_open for blsv_tlock_decrypt, blsv_tlock_open_rounds for
+ * blsv_tlock_decrypt_rounds -- returns for the same arguments; out_cs[i] = msgs[i] XOR stream(K_i, mlen)
+ * with K_i from blsv_tlock_seal / blsv_tlock_seal_rounds, and out_us48 is byte for byte theirs. An item
+ * without a value (a U that does not decode, an item under a sigma that does not decode, a refused scalar)
+ * gets mlen zero bytes where the matching entry point writes BLSV_GT_LEN zero bytes (and BLSV_U_LEN zero
+ * bytes of U when sealing). U or sigma at infinity is not a rejection: E = 1 and the item is masked with
+ * stream(encode(1)), as any other value. Everything else is the matching entry point's, unchanged: ok,
+ * reject_class, sig_class, BLSV_REJ_TLOCK_SIG, BLSV_EINVAL with *sig_class set and no per-item output touched
+ * for a sigma that does not decode, BLSV_ENOGROUP, the refusal of k == 0 (mod r), the caches, and the
+ * counters: each entry point counts in the *_stats of the pass it runs. As there, nothing checks that
+ * sigma is the round's signature: a wrong one decrypts to garbage without any error.
+ *
+ * Host forms: a pass uploads its cnt x mlen input bytes beside what it uploads today and downloads cnt x mlen
+ * output bytes and the class bytes; the staging is the pipeline's (memory contract above, unchanged).
+ * Secrecy (encrypt): K_i alone unmasks message i, so the pass's captured K values are cleared on the device
+ * behind the mask kernel, also when the pass fails, beside the clearing of the scalars and of k_i pk that the
+ * sealing passes do; the host forms clear their staged plaintexts too. No constant-time claim, as above.
+ *
+ * Latency path: the host forms follow the existing switches -- blsv_tlock_decrypt and _decrypt_rounds route
+ * as blsv_tlock_open / _open_rounds do under blsv_set_tlock_lat_max, blsv_tlock_encrypt and _encrypt_rounds as
+ * blsv_tlock_seal / _seal_rounds under blsv_set_tseal_lat_max. The latency kernel runs unchanged and the
+ * mask kernel behind it on the same stream; the path's buffer grows by 2 mlen bytes per item, the download
+ * is mlen bytes per item and the classes, blsv_tlock_lat_stats / blsv_tseal_lat_stats count the call, and
+ * the outputs are byte for byte the batch path's. The _dev forms never route. There is no service entry.
+ *
+ * _dev forms: as the matching _dev entry point (host and device arguments, the stream rule, what is read
+ * back); d_cs / d_msgs / d_out_msgs / d_out_cs are device pointers of any alignment.
+ *
+ * Measured on one MI355X (profiles/tcrypt_bench.json; 1 Mi items, mlen = 32, the fused entry and
+ * the one it fuses alternating call by call, medians, outputs hashed every step): blsv_tlock_decrypt_dev 291.9 ms
+ * against 291.7 ms for blsv_tlock_open_dev (3.59 M plaintexts/s), blsv_tlock_encrypt_dev 84.7 against 84.6 ms for
+ * blsv_tlock_seal_dev (12.38 M plaintexts/s): the fused tail costs nothing measurable. The host form
+ * blsv_tlock_decrypt takes 293.6 ms against 303.0 ms for blsv_tlock_open, which still owes its KDF. On the latency
+ * path a lone decrypt takes 1.53 against 1.49 ms for a lone open, a lone encrypt 1.89 against 1.85 ms for a seal.
+ */
+#define BLSV_KDF_SHA256_CTR 1
+#define BLSV_TLOCK_MSG_MAX 256
+int blsv_tlock_decrypt(blsv_ctx* ctx, const uint8_t* sig96, const uint8_t* us48, const uint8_t* cs, size_t mlen,
+                       size_t n, int kdf, uint8_t* out_msgs, uint8_t* ok, uint8_t* reject_class /*optional*/,
+                       uint8_t* sig_class /*optional*/);
+int blsv_tlock_decrypt_dev(blsv_ctx* ctx, const uint8_t* sig96, const uint8_t* d_us48, const uint8_t* d_cs, size_t mlen,
+                           size_t n, int kdf, uint8_t* d_out_msgs, uint8_t* d_reject_class /*optional*/, void* stream);
+int blsv_tlock_decrypt_rounds(blsv_ctx* ctx, const uint8_t* sigs96, const uint64_t* counts, size_t m,
+                              const uint8_t* us48, const uint8_t* cs, size_t mlen, size_t n, int kdf, uint8_t* out_msgs,
+                              uint8_t* ok, uint8_t* reject_class /*optional, n*/, uint8_t* sig_class /*optional, m*/);
+int blsv_tlock_decrypt_rounds_dev(blsv_ctx* ctx, const uint8_t* sigs96, const uint64_t* counts, size_t m,
+                                  const uint8_t* d_us48, const uint8_t* d_cs, size_t mlen, size_t n, int kdf,
+                                  uint8_t* d_out_msgs, uint8_t* d_reject_class /*optional*/,
+                                  uint8_t* d_sig_class /*optional*/, void* stream);
+int blsv_tlock_encrypt(blsv_ctx* ctx, const uint8_t* pk48, uint64_t round, const uint8_t* scalars32,
+                       const uint8_t* msgs, size_t mlen, size_t n, int kdf, uint8_t* out_us48, uint8_t* out_cs,
+                       uint8_t* ok);
+int blsv_tlock_encrypt_dev(blsv_ctx* ctx, const uint8_t* pk48, uint64_t round, const uint8_t* d_scalars32,
+                           const uint8_t* d_msgs, size_t mlen, size_t n, int kdf, uint8_t* d_out_us48,
+                           uint8_t* d_out_cs, uint8_t* d_ok, void* stream);
+int blsv_tlock_encrypt_rounds(blsv_ctx* ctx, const uint8_t* pk48, const uint64_t* rounds, const uint8_t* scalars32,
+                              const uint8_t* msgs, size_t mlen, size_t n, int kdf, uint8_t* out_us48, uint8_t* out_cs,
+                              uint8_t* ok);
+int blsv_tlock_encrypt_rounds_dev(blsv_ctx* ctx, const uint8_t* pk48, const uint64_t* d_rounds,
+                                  const uint8_t* d_scalars32, const uint8_t* d_msgs, size_t mlen, size_t n, int kdf,
+                                  uint8_t* d_out_us48, uint8_t* d_out_cs, uint8_t* d_ok, void* stream);
 
 /* ---------------------------------------------------------------- thread-safe service
  *

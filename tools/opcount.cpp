@@ -23,6 +23,7 @@
 #include "../drand_amd/csrc/hostlogic.h"
 #include "../drand_amd/csrc/tseal.h"
 #include "../drand_amd/csrc/tsealr.h"
+#include "../drand_amd/csrc/tmask.h"
 
 namespace bls {
 unsigned long long g_fp_mul_count = 0;
@@ -670,6 +671,77 @@ static std::string hex_of(const uint8_t* b, size_t n) {
   return h;
 }
 
+// tmask: the fused tail of timelock encrypt / decrypt (drand_amd/csrc/tmask.h) as the device runs it. stdin:
+// the first line is mlen (1 .. 256), then one item per line, "gt576hex msghex [class]" (class defaults to 0;
+// an item whose class is not 0 gets mlen zero bytes). Prints the masked bytes of every item. "forms_match":
+// the two input forms (the SoA capture in Montgomery form and the encoded bytes), the dword and the byte
+// stores, and the in-place run all give the same bytes, and the guard bytes around every output are intact.
+static int cmd_tmask() {
+  static char buf[4096];
+  if (!fgets(buf, sizeof buf, stdin)) return 2;
+  const unsigned long mlen = strtoul(buf, nullptr, 10);
+  if (mlen < 1 || mlen > (unsigned long)TMASK_MSG_MAX) return 2;
+  std::vector<std::vector<uint8_t>> gts, msgs;
+  std::vector<int> classes;
+  while (fgets(buf, sizeof buf, stdin)) {
+    char* save = nullptr;
+    const char* gh = strtok_r(buf, " \n", &save);
+    if (!gh) continue;
+    const char* mh = strtok_r(nullptr, " \n", &save);
+    const char* ch = strtok_r(nullptr, " \n", &save);
+    if (!mh) return 2;
+    gts.push_back(unhex(gh));
+    msgs.push_back(unhex(mh));
+    classes.push_back(ch ? atoi(ch) : 0);
+    if (gts.back().size() != (size_t)TMASK_GT_LEN || msgs.back().size() != mlen) return 2;
+  }
+  const size_t n = gts.size();
+  if (!n) return 2;
+  // the SoA capture as the final exponentiation leaves it: slot 11 - k holds coefficient k, Montgomery form
+  std::vector<uint32_t> E(144 * n), enc(144 * n);
+  for (size_t i = 0; i < n; i++) {
+    for (int k = 0; k < 12; k++) st_fp(E.data(), n, i, 11 - k, fp_to_mont(fp_raw_from_be48(gts[i].data() + 48 * k)));
+    memcpy(enc.data() + 144 * i, gts[i].data(), TMASK_GT_LEN);
+  }
+  constexpr size_t G = 8;  // guard bytes (a multiple of 4: the dword runs stay aligned)
+  auto run = [&](int form, bool words, bool in_place) {
+    // items with their guards, 4-byte aligned through the uint32 backing
+    const size_t stride = mlen;
+    std::vector<uint32_t> back((2 * G + n * stride) / 4 + 2);
+    uint8_t* base = (uint8_t*)back.data();
+    memset(base, 0xAA, 2 * G + n * stride);
+    std::vector<uint32_t> inb((n * stride) / 4 + 2);
+    uint8_t* in = in_place ? base + G : (uint8_t*)inb.data();
+    for (size_t i = 0; i < n; i++) memcpy(in + i * stride, msgs[i].data(), mlen);
+    for (size_t i = 0; i < n; i++) {
+      const bool good = classes[i] == 0;
+      uint32_t mid[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+      if (good) {
+        if (form == 0)
+          tmask_midstate(mid, [&](int k) { return tmask_coef_soa(E.data(), n, i, k); });
+        else
+          tmask_midstate(mid, [&](int k) { return tmask_coef_enc(enc.data() + 144 * i, k); });
+      }
+      if (words)
+        tmask_apply<true>(mid, good, in + i * stride, base + G + i * stride, (uint32_t)mlen);
+      else
+        tmask_apply<false>(mid, good, in + i * stride, base + G + i * stride, (uint32_t)mlen);
+    }
+    std::vector<uint8_t> out(base + G, base + G + n * stride);
+    for (size_t g = 0; g < G; g++)
+      if (base[g] != 0xAA || base[G + n * stride + g] != 0xAA) out.clear();  // a guard was written
+    return out;
+  };
+  const std::vector<uint8_t> out = run(0, false, false);
+  bool match = !out.empty() && run(1, false, false) == out && run(0, false, true) == out;
+  if (mlen % 4 == 0) match &= run(0, true, false) == out && run(1, true, true) == out;
+  printf("{\"mlen\": %lu, \"forms_match\": %s, \"out\": [", mlen, match ? "true" : "false");
+  for (size_t i = 0; i < n && !out.empty(); i++)
+    printf("%s\"%s\"", i ? ", " : "", hex_of(out.data() + i * mlen, mlen).c_str());
+  printf("]}\n");
+  return match ? 0 : 1;
+}
+
 // tseal <pk48hex> <round>: the timelock sealing (drand_amd/csrc/tseal.h) as the device runs it -- the base
 // B = e(pk, H(MessageV2(round)))^3 through the opening's own forms (hash, prepared line table, f pass,
 // final exponentiation), the tables T1 (multiples of G1) and T2 (powers of B), then per scalar (stdin, 32
@@ -1093,6 +1165,7 @@ static int cmd_subgroup() {
 int main(int argc, char** argv) {
   if (argc == 2 && !strcmp(argv[1], "subgroup")) return cmd_subgroup();
   if (argc == 3 && !strcmp(argv[1], "tlock")) return cmd_tlock(argv[2]);
+  if (argc == 2 && !strcmp(argv[1], "tmask")) return cmd_tmask();
   if (argc == 4 && !strcmp(argv[1], "tseal")) return cmd_tseal(argv[2], strtoull(argv[3], nullptr, 10));
   if (argc == 3 && !strcmp(argv[1], "tsealr")) return cmd_tsealr(argv[2]);
   if (argc >= 4 && !strcmp(argv[1], "tlockr")) return cmd_tlockr(argc - 2, argv + 2);
