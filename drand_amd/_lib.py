@@ -33,9 +33,12 @@ REJ_NOT_IN_SUBGROUP = 6
 REJ_PAIRING = 7
 REJ_SHARE_INDEX = 8
 REJ_TLOCK_SIG = 9
+REJ_TLOCK_AUTH = 10  # BLSV_REJ_TLOCK_AUTH: the item failed the re-encryption check of blsv_tlock_decrypt_auth*
 
 KDF_SHA256_CTR = 1     # BLSV_KDF_SHA256_CTR: callers.kdf_sha256_ctr on the device
 TLOCK_MSG_MAX = 256    # BLSV_TLOCK_MSG_MAX: the longest message of blsv_tlock_decrypt* / blsv_tlock_encrypt*
+SEED_LEN = 32          # BLSV_SEED_LEN: the seed of an authenticated ciphertext (blsv_tlock_encrypt_auth*)
+V_LEN = 32             # BLSV_V_LEN: its masked seed
 
 REJ_NAMES = {
     REJ_OK: "ok",
@@ -48,6 +51,7 @@ REJ_NAMES = {
     REJ_PAIRING: "bls: invalid signature",
     REJ_SHARE_INDEX: "tbls: invalid signature share",
     REJ_TLOCK_SIG: "timelock: the round signature did not decode",
+    REJ_TLOCK_AUTH: "timelock: the ciphertext failed its authentication check",
 }
 
 u8p = ctypes.POINTER(ctypes.c_uint8)
@@ -139,6 +143,18 @@ SIGNATURES = {
     "blsv_tlock_encrypt_dev": (ctypes.c_int, [vp, u8p, ctypes.c_uint64, vp, vp, sz, sz, ctypes.c_int, vp, vp, vp, vp]),
     "blsv_tlock_encrypt_rounds": (ctypes.c_int, [vp, u8p, u64p, u8p, u8p, sz, sz, ctypes.c_int, u8p, u8p, u8p]),
     "blsv_tlock_encrypt_rounds_dev": (ctypes.c_int, [vp, u8p, vp, vp, vp, sz, sz, ctypes.c_int, vp, vp, vp, vp]),
+    "blsv_tlock_encrypt_auth": (ctypes.c_int, [vp, u8p, ctypes.c_uint64, u8p, u8p, sz, sz, ctypes.c_int, u8p, u8p, u8p,
+                                                u8p]),
+    "blsv_tlock_encrypt_auth_dev": (ctypes.c_int, [vp, u8p, ctypes.c_uint64, vp, vp, sz, sz, ctypes.c_int, vp, vp, vp, vp,
+                                                    vp]),
+    "blsv_tlock_encrypt_auth_rounds": (ctypes.c_int, [vp, u8p, u64p, u8p, u8p, sz, sz, ctypes.c_int, u8p, u8p, u8p, u8p]),
+    "blsv_tlock_encrypt_auth_rounds_dev": (ctypes.c_int, [vp, u8p, vp, vp, vp, sz, sz, ctypes.c_int, vp, vp, vp, vp, vp]),
+    "blsv_tlock_decrypt_auth": (ctypes.c_int, [vp, u8p, u8p, u8p, u8p, sz, sz, ctypes.c_int, u8p, u8p, u8p, u8p]),
+    "blsv_tlock_decrypt_auth_dev": (ctypes.c_int, [vp, u8p, vp, vp, vp, sz, sz, ctypes.c_int, vp, vp, vp]),
+    "blsv_tlock_decrypt_auth_rounds": (ctypes.c_int, [vp, u8p, u64p, sz, u8p, u8p, u8p, sz, sz, ctypes.c_int, u8p, u8p,
+                                                       u8p, u8p]),
+    "blsv_tlock_decrypt_auth_rounds_dev": (ctypes.c_int, [vp, u8p, u64p, sz, vp, vp, vp, sz, sz, ctypes.c_int, vp, vp, vp,
+                                                           vp]),
 }
 
 _lib = None

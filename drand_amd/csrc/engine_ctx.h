@@ -1,5 +1,5 @@
 // Internal to libblsverify.so (never installed, no C ABI): the context object and the helpers the
-// C-ABI entry points (blsverify.cpp, verify.cpp, threshold.cpp, tlock.cpp, tlockr.cpp, tseal.cpp, tsealr.cpp, tcrypt.cpp, testhooks.cpp; their shared
+// C-ABI entry points (blsverify.cpp, verify.cpp, threshold.cpp, tlock.cpp, tlockr.cpp, tseal.cpp, tsealr.cpp, tcrypt.cpp, tauth.cpp, testhooks.cpp; their shared
 // internals are host_internal.h) and the thread-safe service (service.cpp) share.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -146,6 +146,32 @@ static_assert(2 + 4 + 4 + 4 * blsk::kTlockTileWords <= 4 * 3 * blsk::F_WORDS,
 // A device form reads and writes the caller's buffers in place. No storage of its own.
 static_assert(2 * BLSV_TLOCK_MSG_MAX <= 4 * blsk::F_WORDS,
               "timelock in one call: a pass's input and output bytes do not fit the F staging");
+
+// Authenticated timelock (blsv_tlock_encrypt_auth* / blsv_tlock_decrypt_auth*, tauth.cpp, k_tauth.hip): each of
+// the four timelock passes above with its last stage swapped once more -- k_tauth_seal_tail / k_tauth_open_tail
+// read the captured values in HQ where k_tmask read them. Nothing else in a pass moves, and the opening tail
+// also reads what the pass left behind the final exponentiation: the decoded U table in H / h_inf and the
+// class bytes in s_inf (it writes BLSV_REJ_TLOCK_AUTH there). The passes always run on device pointers. What
+// is not a stage's own lives in ONE device buffer of the feature's (tauth_state::buf, hostlogic.h
+// tauth_layout), sized for a pass of cnt <= cap items and allocated at the first authenticated call -- the
+// pipeline staging is not used for it: S holds the P table in a pass across rounds and U bytes or signatures
+// in an opening, and F is the exponentiation's in three of the four passes, so no one buffer is free in all:
+//   a device form, encrypting    the derived scalars (32 bytes per item) that k_tauth_derive writes and the
+//                                sealing kernels read, cleared behind them, also when the pass failed
+//   a host form, encrypting      the seeds, the derived scalars and the plaintexts ([0, secret): cleared behind
+//                                the kernels, also when the pass failed; seeds and plaintexts are uploaded
+//                                straight from the caller's memory), the rounds, and the pass's U, V, W and ok
+//                                bytes, from where the download takes them
+//   a host form, decrypting      the pass's U, V and W bytes, its message bytes and its class bytes
+// A device form that decrypts stages nothing. HQ's captured K is cleared as in blsv_tlock_encrypt (mask_wipe).
+// T1 is the sealing's (tseal_state::t1), built on first use by whichever call needs it first.
+static_assert(BLSV_SEED_LEN == 32 && BLSV_V_LEN == 32 && BLSV_SCALAR_LEN == 32,
+              "authenticated timelock: tauth_layout's rows of seeds, V bytes and scalars");
+static_assert(blsk::kTauthSeedLen == BLSV_SEED_LEN && blsk::kTauthVLen == BLSV_V_LEN,
+              "authenticated timelock: the header's sizes are the kernels'");
+static_assert(32 + 32 + 8 + BLSV_U_LEN + 32 + 2 * BLSV_TLOCK_MSG_MAX + 1 + 16 <= 1024,
+              "authenticated timelock: tauth_fits bounds a pass's staging by 1 KiB per item");
+static_assert(blsk::G1_WORDS <= blsk::H_WORDS, "authenticated timelock: the U table the opening tail reads is the pass's own in H");
 
 struct DBuf {
   void* p = nullptr;
@@ -382,6 +408,12 @@ struct tseal_lat_state {
   std::vector<uint8_t> up, down;  // the scalars in `up` are cleared before the entry returns
 };
 
+// Authenticated timelock (blsv_tlock_encrypt_auth* / blsv_tlock_decrypt_auth*): the one buffer of its own
+// (hostlogic.h tauth_layout; the plan is above). No cache and no counter: a call counts in the pass it runs.
+struct tauth_state {
+  DBuf buf;
+};
+
 struct blsv_ctx {
   int device = 0;
   bool prof = false;
@@ -449,6 +481,7 @@ struct blsv_ctx {
   tlockr_state tlockr;
   tlock_lat_state tlock_lat;
   tseal_lat_state tseal_lat;
+  tauth_state tauth;
 };
 
 #define HIPCHK(ctx, expr)                                                             \

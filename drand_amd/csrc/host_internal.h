@@ -1,5 +1,5 @@
 // Internal to the HIP-side host units of libblsverify.so (blsverify.cpp, verify.cpp, threshold.cpp,
-// tlock.cpp, tlockr.cpp, tseal.cpp, tsealr.cpp, tcrypt.cpp, testhooks.cpp): the pinned small copies, stage timing, the typed view of the pipeline
+// tlock.cpp, tlockr.cpp, tseal.cpp, tsealr.cpp, tcrypt.cpp, tauth.cpp, testhooks.cpp): the pinned small copies, stage timing, the typed view of the pipeline
 // staging with its launch wrappers, and the one pass loop every verification entry point runs.
 #pragma once
 #include <functional>
@@ -175,6 +175,47 @@ int mask_tail(blsv_ctx* c, const MaskTail& mk, const uint8_t* flag, uint8_t good
 // Behind the tail of an encrypting pass, also when it failed: clears the K capture in HQ and a host form's
 // staged plaintexts in F
 hipError_t mask_wipe(blsv_ctx* c, const MaskTail& mk, size_t cnt, hipStream_t st);
+
+// ---- tauth.cpp: the authenticated tail of the four timelock passes (blsv_tlock_encrypt_auth* /
+// blsv_tlock_decrypt_auth*, k_tauth.hip, tauth.h) in place of the mask tail. Off (the default): the pass is
+// byte for byte what it was. On: the pass runs on device pointers (MaskTail::host is false: a host form stages
+// its bytes in the feature's own buffer, engine_ctx.h) and mk.mlen is the message length.
+struct AuthTail {
+  bool on = false;
+  const uint8_t* vs = nullptr;     // decrypt: the call's n x 32 V bytes
+  const uint8_t* seeds = nullptr;  // encrypt: the call's n x 32 seeds
+  uint8_t* out_vs = nullptr;       // encrypt: the call's n x 32 V bytes
+  AuthTail at(size_t base) const {  // the part of the pass that starts at item base
+    AuthTail a = *this;
+    if (vs) a.vs += base * 32;
+    if (seeds) a.seeds += base * 32;
+    if (out_vs) a.out_vs += base * 32;
+    return a;
+  }
+};
+// The tail of an opening pass of cnt items: E in HQ, the decoded U table in H / h_inf, the class bytes in
+// s_inf (read and written); ws = the pass's cnt x mlen W bytes, d_out = cnt x mlen message bytes
+int auth_open_tail(blsv_ctx* c, const AuthTail& au, const MaskTail& mk, size_t cnt, const uint8_t* ws, uint8_t* d_out,
+                   hipStream_t st);
+// The tail of a sealing pass of cnt items: K in HQ, cls = launch_tseal_u's class bytes; msgs = the pass's
+// cnt x mlen message bytes, d_out_ws = cnt x mlen W bytes
+int auth_seal_tail(blsv_ctx* c, const AuthTail& au, const MaskTail& mk, const uint8_t* cls, size_t cnt,
+                   const uint8_t* msgs, uint8_t* d_out_ws, hipStream_t st);
+
+// ---- the passes of the four timelock units, shared with tauth.cpp (each is described where it is defined)
+int tlock_prepare_sig(blsv_ctx* c, const uint8_t* sig96, hipStream_t st, uint8_t* sig_class);
+int tlock_passes(blsv_ctx* c, bool host, const uint8_t* us, size_t n, uint8_t* out, uint8_t* cls, hipStream_t st,
+                 const MaskTail& mk = MaskTail(), const uint8_t* mk_in = nullptr, const AuthTail& au = AuthTail());
+int rounds_passes(blsv_ctx* c, bool host, const uint8_t* sigs96, const uint64_t* counts, size_t m, const uint8_t* us,
+                  size_t n, uint8_t* out, uint8_t* cls, uint8_t* d_sig_class, hipStream_t st,
+                  const MaskTail& mk = MaskTail(), const uint8_t* mk_in = nullptr, const AuthTail& au = AuthTail());
+int seal_prepare(blsv_ctx* c, const uint8_t* pk48, uint64_t round, size_t n, hipStream_t st);
+int seal_passes(blsv_ctx* c, bool host, const uint8_t* scalars, size_t n, uint8_t* us, uint8_t* gt, uint8_t* ok,
+                hipStream_t st, const MaskTail& mk = MaskTail(), const uint8_t* mk_in = nullptr,
+                const AuthTail& au = AuthTail());
+int sealr_passes(blsv_ctx* c, bool host, const uint64_t* rounds, const uint8_t* scalars, size_t n, uint8_t* us,
+                 uint8_t* gt, uint8_t* ok, hipStream_t st, const MaskTail& mk = MaskTail(),
+                 const uint8_t* mk_in = nullptr, const AuthTail& au = AuthTail());
 
 // ---- tlock.cpp: a host call of n >= 1 items on the latency path (hostlogic.h tlock_lat_routes). The m
 // signatures, item i under sig_of[i] (null: all under signature 0), the n_idle signatures idle[] classed

@@ -305,6 +305,31 @@ inline bool tcrypt_fits(int kdf, size_t mlen, size_t n) {
          n <= SIZE_MAX / BLSV_GT_LEN;
 }
 
+// blsv_tlock_encrypt_auth* / blsv_tlock_decrypt_auth*: tcrypt_fits, and the byte counts of the feature's own
+// staging (tauth_layout, below 1 KiB per item) fit size_t
+inline bool tauth_fits(int kdf, size_t mlen, size_t n) { return tcrypt_fits(kdf, mlen, n) && n <= SIZE_MAX / 1024; }
+// ... and what a pass of cnt items of mlen bytes keeps in that staging (engine_ctx.h "authenticated timelock").
+// [0, secret) is what an encrypting call clears behind the kernels: the seeds, the derived scalars and the
+// plaintexts. A device form uses the scalar row alone. Every part starts on a multiple of 8.
+struct TauthLayout {
+  size_t o_seeds, o_scalars, o_in, secret, o_rounds, o_us, o_vs, o_out, o_flag, total;
+};
+inline TauthLayout tauth_layout(size_t cnt, size_t mlen) {
+  const auto up8 = [](size_t v) { return (v + 7) & ~size_t(7); };
+  TauthLayout l;
+  l.o_seeds = 0;
+  l.o_scalars = l.o_seeds + cnt * 32;
+  l.o_in = l.o_scalars + cnt * BLSV_SCALAR_LEN;  // plaintexts (encrypt) or W bytes (decrypt)
+  l.secret = up8(l.o_in + cnt * mlen);
+  l.o_rounds = l.secret;
+  l.o_us = l.o_rounds + cnt * 8;
+  l.o_vs = l.o_us + cnt * BLSV_U_LEN;
+  l.o_out = l.o_vs + cnt * 32;  // W bytes (encrypt) or messages (decrypt)
+  l.o_flag = up8(l.o_out + cnt * mlen);  // ok bytes (encrypt) or class bytes (decrypt)
+  l.total = l.o_flag + cnt;
+  return l;
+}
+
 // ---------------------------------------------------------------- blsv_tlock_open_rounds*: the plan
 // m round signatures, round j owning counts[j] consecutive items of the n packed ones. Whether the call's
 // arguments are consistent and every byte count of it fits size_t: sum counts == n (the sum itself must

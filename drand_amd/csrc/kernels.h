@@ -181,6 +181,23 @@ void launch_tmask(const uint32_t* E, const uint8_t* flag, uint8_t good, size_t c
 void launch_tmask_encoded(const uint8_t* gt576, const uint8_t* flag, uint8_t good, size_t cnt, const uint8_t* in,
                           uint8_t* out, size_t mlen, hipStream_t st);
 
+// ---- authenticated timelock (k_tauth.hip, tauth.h): one lane per item; cnt x mlen packed bytes of any
+// alignment as above (dwords move only when the message pointers and mlen are all multiples of 4).
+// derive: seeds (cnt x 32) and msgs -> scalars (cnt x 32 bytes big-endian, k = H3(seed, msg) mod r; zeros for a
+// derived zero). seal_tail: E = the captured K (SoA of stride cnt), cls = launch_tseal_u's class bytes ->
+// out_vs (cnt x 32) and out_ws, zeros where cls != 0; out_ws == msgs is allowed. open_tail: E = the captured
+// values, U / u_inf = launch_decompress_g1's table of the pass, T1 = launch_tseal_g1_table's -> out = the
+// messages of the items that pass the re-encryption check, zeros for every other; cls[i] becomes
+// BLSV_REJ_TLOCK_AUTH where it was 0 and the check failed; out == ws is allowed.
+constexpr size_t kTauthSeedLen = 32, kTauthVLen = 32;
+void launch_tauth_derive(const uint8_t* seeds, const uint8_t* msgs, size_t cnt, size_t mlen, uint8_t* scalars,
+                         hipStream_t st);
+void launch_tauth_seal_tail(const uint32_t* E, const uint8_t* cls, size_t cnt, const uint8_t* seeds, const uint8_t* msgs,
+                            size_t mlen, uint8_t* out_vs, uint8_t* out_ws, hipStream_t st);
+void launch_tauth_open_tail(const uint32_t* E, const uint32_t* U, const uint8_t* u_inf, uint8_t* cls, size_t cnt,
+                            const uint32_t* T1, const uint8_t* vs, const uint8_t* ws, size_t mlen, uint8_t* out,
+                            hipStream_t st);
+
 // ---- latency path (k_lat.hip): one workgroup per item, the whole verification; writes cls[i] (REJ_*)
 int lat_trace_read(uint64_t* out, int n, hipStream_t st);  // phase marks of item 0 (wteam.h WV_MARK)
 int lat_trace_clear(hipStream_t st);

@@ -9,7 +9,7 @@
 
 // Decodes and prepares sigma on st unless it is the cached one; its class is read back (the one
 // synchronisation of a call, and only on a new sigma).
-static int tlock_prepare_sig(blsv_ctx* c, const uint8_t* sig96, hipStream_t st, uint8_t* sig_class) {
+int tlock_prepare_sig(blsv_ctx* c, const uint8_t* sig96, hipStream_t st, uint8_t* sig_class) {
   tlock_state& t = c->tlock;
   if (!t.valid || memcmp(t.sig, sig96, 96) != 0) {
     t.valid = false;
@@ -42,9 +42,10 @@ static int tlock_prepare_sig(blsv_ctx* c, const uint8_t* sig96, hipStream_t st, 
 
 // One pass of cnt <= cap items: d_us (cnt x 48 bytes) -> d_out (cnt x 576 bytes), classes in s_inf. With a
 // mask tail (mk.mlen != 0; blsv_tlock_decrypt*) the encoding is replaced by the mask kernel over the pass's
-// input bytes mk_in: d_out gets cnt x mlen bytes.
+// input bytes mk_in: d_out gets cnt x mlen bytes. With an authenticated tail (au.on; blsv_tlock_decrypt_auth*,
+// device pointers only) mk_in is the pass's W bytes and the tail also writes BLSV_REJ_TLOCK_AUTH into s_inf.
 static int tlock_pass(blsv_ctx* c, const uint8_t* d_us, size_t cnt, uint8_t* d_out, uint8_t* d_cls_out, hipStream_t st,
-                      const MaskTail& mk = MaskTail(), const uint8_t* mk_in = nullptr) {
+                      const MaskTail& mk = MaskTail(), const uint8_t* mk_in = nullptr, const AuthTail& au = AuthTail()) {
   const tlock_state& t = c->tlock;
   const Staging w = staging(c);
   uint32_t* U = w.H;
@@ -65,7 +66,10 @@ static int tlock_pass(blsv_ctx* c, const uint8_t* d_us, size_t cnt, uint8_t* d_o
     // the values are captured in HQ, so the park stays in LN (a timelock pass stages no lines)
     blsk::launch_final_exp(w.F, w.FW, cnt, 0, cnt, w.cls, st, w.LN, w.HQ);
   }
-  if (mk.mlen) {
+  if (au.on) {  // the authenticated tail: the U table is still in H / h_inf
+    const int rc = auth_open_tail(c, au, mk, cnt, mk_in, d_out, st);
+    if (rc) return rc;
+  } else if (mk.mlen) {
     const int rc = mask_tail(c, mk, ucls, BLSV_REJ_OK, cnt, mk_in, d_out, st);
     if (rc) return rc;
   } else {
@@ -81,8 +85,8 @@ static int tlock_pass(blsv_ctx* c, const uint8_t* d_us, size_t cnt, uint8_t* d_o
 // S, its encoded values come back through F, and each pass ends with the download's synchronisation.
 // With a mask tail, mk_in is the call's n x mlen input bytes and out receives n x mlen bytes; a host call's
 // pass stages both in F (mask_tail).
-static int tlock_passes(blsv_ctx* c, bool host, const uint8_t* us, size_t n, uint8_t* out, uint8_t* cls, hipStream_t st,
-                        const MaskTail& mk = MaskTail(), const uint8_t* mk_in = nullptr) {
+int tlock_passes(blsv_ctx* c, bool host, const uint8_t* us, size_t n, uint8_t* out, uint8_t* cls, hipStream_t st,
+                 const MaskTail& mk, const uint8_t* mk_in, const AuthTail& au) {
   int rc = ensure_workspace(c, n);
   if (rc) return rc;
   const size_t out_len = mk.mlen ? mk.mlen : BLSV_GT_LEN;
@@ -98,7 +102,7 @@ static int tlock_passes(blsv_ctx* c, bool host, const uint8_t* us, size_t n, uin
       if (rc) return rc;
       HIPCHK(c, download_sync(c, {{pass_out, d_out, cnt * out_len}, {cls + base, c->s_inf.p, cnt}}));
     } else {
-      rc = tlock_pass(c, pass_us, cnt, pass_out, cls ? cls + base : nullptr, st, mk, pass_in);
+      rc = tlock_pass(c, pass_us, cnt, pass_out, cls ? cls + base : nullptr, st, mk, pass_in, au.at(base));
       if (rc) return rc;
     }
   }

@@ -67,10 +67,11 @@ static int rounds_decode(blsv_ctx* c, const uint8_t* sigs96, const std::vector<u
 
 // One pass: d_us (cnt x 48 bytes) -> d_out (cnt x 576 bytes), the items' classes in s_inf. With a mask tail
 // (mk.mlen != 0; blsv_tlock_decrypt_rounds*) the encoding is replaced by the mask kernel over the pass's input
-// bytes mk_in: d_out gets cnt x mlen bytes.
+// bytes mk_in: d_out gets cnt x mlen bytes. An authenticated tail (au.on; blsv_tlock_decrypt_auth_rounds*) as in
+// tlock.cpp's pass.
 static int rounds_pass(blsv_ctx* c, const uint8_t* sigs96, const TlockRoundsPass& p, const uint8_t* d_us, uint8_t* d_out,
                        uint8_t* d_cls_out, uint8_t* d_sig_class, std::vector<uint8_t>& tmp, hipStream_t st,
-                       const MaskTail& mk, const uint8_t* mk_in) {
+                       const MaskTail& mk, const uint8_t* mk_in, const AuthTail& au = AuthTail()) {
   const Staging w = staging(c);
   const RoundsFw fw = rounds_fw(c);
   const size_t cnt = p.cnt, M = p.sig_j.size();
@@ -109,7 +110,10 @@ static int rounds_pass(blsv_ctx* c, const uint8_t* sigs96, const TlockRoundsPass
     // plan in it read too, is the exponentiation's scratch again
     blsk::launch_final_exp(w.F, w.FW, cnt, 0, cnt, w.cls, st, w.LN, w.HQ);
   }
-  if (mk.mlen) {
+  if (au.on) {  // the authenticated tail: the U table is still in H / h_inf
+    const int rc = auth_open_tail(c, au, mk, cnt, mk_in, d_out, st);
+    if (rc) return rc;
+  } else if (mk.mlen) {
     const int rc = mask_tail(c, mk, ucls, BLSV_REJ_OK, cnt, mk_in, d_out, st);
     if (rc) return rc;
   } else {
@@ -126,9 +130,9 @@ static int rounds_pass(blsv_ctx* c, const uint8_t* sigs96, const TlockRoundsPass
 // back through F, and each pass ends with the download's synchronisation.
 // With a mask tail, mk_in is the call's n x mlen input bytes and out receives n x mlen bytes; a host call's
 // pass stages both in F (mask_tail).
-static int rounds_passes(blsv_ctx* c, bool host, const uint8_t* sigs96, const uint64_t* counts, size_t m,
-                         const uint8_t* us, size_t n, uint8_t* out, uint8_t* cls, uint8_t* d_sig_class, hipStream_t st,
-                         const MaskTail& mk = MaskTail(), const uint8_t* mk_in = nullptr) {
+int rounds_passes(blsv_ctx* c, bool host, const uint8_t* sigs96, const uint64_t* counts, size_t m, const uint8_t* us,
+                  size_t n, uint8_t* out, uint8_t* cls, uint8_t* d_sig_class, hipStream_t st, const MaskTail& mk,
+                  const uint8_t* mk_in, const AuthTail& au) {
   int rc = rounds_begin(c, m, n, st);
   if (rc) return rc;
   TlockRoundsCursor cur;
@@ -146,7 +150,8 @@ static int rounds_passes(blsv_ctx* c, bool host, const uint8_t* sigs96, const ui
       if (rc) return rc;
       HIPCHK(c, download_sync(c, {{pass_out, d_out, p.cnt * out_len}, {cls + p.base, c->s_inf.p, p.cnt}}));
     } else {
-      rc = rounds_pass(c, sigs96, p, pass_us, pass_out, cls ? cls + p.base : nullptr, d_sig_class, tmp, st, mk, pass_in);
+      rc = rounds_pass(c, sigs96, p, pass_us, pass_out, cls ? cls + p.base : nullptr, d_sig_class, tmp, st, mk, pass_in,
+                       au.at(p.base));
       if (rc) return rc;
     }
   }

@@ -12,7 +12,7 @@ static uint32_t* seal_line_tab(const Staging& w) { return w.LN + blsk::FEXP_PARK
 // Builds T1 once, and B with T2 unless (key, round) is the cached base. The key's class is read back
 // (the one synchronisation of a call, and only on a new base); a key that does not decode or is the
 // point at infinity returns BLSV_EINVAL before anything else runs.
-static int seal_prepare(blsv_ctx* c, const uint8_t* pk48, uint64_t round, size_t n, hipStream_t st) {
+int seal_prepare(blsv_ctx* c, const uint8_t* pk48, uint64_t round, size_t n, hipStream_t st) {
   tseal_state& t = c->tseal;
   if (t.valid && t.round == round && memcmp(t.pk, pk48, 48) == 0) return BLSV_OK;
   int rc = ensure_workspace(c, std::max(n, size_t(1)));  // the call's passes find it allocated
@@ -64,9 +64,10 @@ static int seal_prepare(blsv_ctx* c, const uint8_t* pk48, uint64_t round, size_t
 
 // One pass of cnt <= cap items: d_scalars (cnt x 32 bytes) -> d_us (cnt x 48), d_gt (cnt x 576), d_ok (cnt). With
 // a mask tail (mk.mlen != 0; blsv_tlock_encrypt*) the encoding is replaced by the mask kernel over the pass's
-// message bytes mk_in: d_gt gets cnt x mlen ciphertext bytes.
+// message bytes mk_in: d_gt gets cnt x mlen ciphertext bytes. With an authenticated tail (au.on;
+// blsv_tlock_encrypt_auth*, device pointers only) d_scalars is the derived-scalar row and d_gt gets the W bytes.
 static int seal_pass(blsv_ctx* c, const uint8_t* d_scalars, size_t cnt, uint8_t* d_us, uint8_t* d_gt, uint8_t* d_ok,
-                     hipStream_t st, const MaskTail& mk, const uint8_t* mk_in) {
+                     hipStream_t st, const MaskTail& mk, const uint8_t* mk_in, const AuthTail& au = AuthTail()) {
   const tseal_state& t = c->tseal;
   const Staging w = staging(c);
   uint8_t* cls = w.s_inf;
@@ -75,7 +76,10 @@ static int seal_pass(blsv_ctx* c, const uint8_t* d_scalars, size_t cnt, uint8_t*
     blsk::launch_tseal_u(t.t1.as<uint32_t>(), d_scalars, cnt, d_us, d_ok, cls, st);
     blsk::launch_tseal_gt(t.t2.as<uint32_t>(), d_scalars, cls, cnt, w.HQ, st);
   }
-  if (mk.mlen) {
+  if (au.on) {
+    const int rc = auth_seal_tail(c, au, mk, cls, cnt, mk_in, d_gt, st);
+    if (rc) return rc;
+  } else if (mk.mlen) {
     const int rc = mask_tail(c, mk, cls, BLSV_REJ_OK, cnt, mk_in, d_gt, st);
     if (rc) return rc;
   } else {
@@ -92,8 +96,8 @@ static int seal_pass(blsv_ctx* c, const uint8_t* d_scalars, size_t cnt, uint8_t*
 // message bytes and gt receives n x mlen ciphertext bytes; a host call's pass stages both in F (mask_tail),
 // and the captured K (with a host call's staged plaintexts) is cleared behind the kernel, also when the
 // pass failed.
-static int seal_passes(blsv_ctx* c, bool host, const uint8_t* scalars, size_t n, uint8_t* us, uint8_t* gt, uint8_t* ok,
-                       hipStream_t st, const MaskTail& mk = MaskTail(), const uint8_t* mk_in = nullptr) {
+int seal_passes(blsv_ctx* c, bool host, const uint8_t* scalars, size_t n, uint8_t* us, uint8_t* gt, uint8_t* ok,
+                hipStream_t st, const MaskTail& mk, const uint8_t* mk_in, const AuthTail& au) {
   int rc = ensure_workspace(c, n);
   if (rc) return rc;
   const size_t out_len = mk.mlen ? mk.mlen : BLSV_GT_LEN;
@@ -114,7 +118,7 @@ static int seal_passes(blsv_ctx* c, bool host, const uint8_t* scalars, size_t n,
                                   {ok + base, c->h_inf.p, cnt}}));
     } else {
       rc = seal_pass(c, scalars + base * BLSV_SCALAR_LEN, cnt, us + base * BLSV_U_LEN, gt + base * out_len, ok + base,
-                     st, mk, pass_in);
+                     st, mk, pass_in, au.at(base));
       const hipError_t wipe_k = mask_wipe(c, mk, cnt, st);
       if (rc) return rc;
       HIPCHK(c, wipe_k);

@@ -48,9 +48,10 @@ int sealr_prepare(blsv_ctx* c, const uint8_t* pk48, size_t n, hipStream_t st) {
 // One pass of cnt <= cap items: d_rounds (cnt), d_scalars (cnt x 32 bytes) -> d_us (cnt x 48), d_gt
 // (cnt x 576), d_ok (cnt). The points P_i wait in S (seal_rounds_layout) for the lines pass. With a mask tail
 // (mk.mlen != 0; blsv_tlock_encrypt_rounds*) the encoding is replaced by the mask kernel over the pass's message
-// bytes mk_in: d_gt gets cnt x mlen ciphertext bytes.
+// bytes mk_in: d_gt gets cnt x mlen ciphertext bytes. An authenticated tail (au.on) as in tseal.cpp's pass.
 static int sealr_pass(blsv_ctx* c, const uint64_t* d_rounds, const uint8_t* d_scalars, size_t cnt, uint8_t* d_us,
-                      uint8_t* d_gt, uint8_t* d_ok, hipStream_t st, const MaskTail& mk, const uint8_t* mk_in) {
+                      uint8_t* d_gt, uint8_t* d_ok, hipStream_t st, const MaskTail& mk, const uint8_t* mk_in,
+                      const AuthTail& au = AuthTail()) {
   const Staging w = staging(c);
   uint32_t* P = w.S + seal_rounds_layout(cnt).o_p / 4;
   uint8_t* cls = w.s_inf;
@@ -76,7 +77,10 @@ static int sealr_pass(blsv_ctx* c, const uint64_t* d_rounds, const uint8_t* d_sc
     // the lines are read: the park goes to LN and the values are captured in HQ, as in an opening
     blsk::launch_final_exp(w.F, w.FW, cnt, 0, cnt, w.cls, st, w.LN, w.HQ);
   }
-  if (mk.mlen) {
+  if (au.on) {
+    const int rc = auth_seal_tail(c, au, mk, cls, cnt, mk_in, d_gt, st);
+    if (rc) return rc;
+  } else if (mk.mlen) {
     const int rc = mask_tail(c, mk, cls, BLSV_REJ_OK, cnt, mk_in, d_gt, st);
     if (rc) return rc;
   } else {
@@ -93,9 +97,8 @@ static int sealr_pass(blsv_ctx* c, const uint64_t* d_rounds, const uint8_t* d_sc
 // kernels that read it, also when the pass failed. With a mask tail, mk_in is the call's n x mlen message bytes
 // and gt receives n x mlen ciphertext bytes; a host call's pass stages both in F (mask_tail), and the captured
 // K (with a host call's staged plaintexts) is cleared with the P table.
-static int sealr_passes(blsv_ctx* c, bool host, const uint64_t* rounds, const uint8_t* scalars, size_t n, uint8_t* us,
-                        uint8_t* gt, uint8_t* ok, hipStream_t st, const MaskTail& mk = MaskTail(),
-                        const uint8_t* mk_in = nullptr) {
+int sealr_passes(blsv_ctx* c, bool host, const uint64_t* rounds, const uint8_t* scalars, size_t n, uint8_t* us,
+                 uint8_t* gt, uint8_t* ok, hipStream_t st, const MaskTail& mk, const uint8_t* mk_in, const AuthTail& au) {
   int rc = ensure_workspace(c, n);
   if (rc) return rc;
   const size_t out_len = mk.mlen ? mk.mlen : BLSV_GT_LEN;
@@ -114,7 +117,7 @@ static int sealr_passes(blsv_ctx* c, bool host, const uint64_t* rounds, const ui
                                          S + l.o_ok, st, mk, pass_in);
     } else {
       rc = sealr_pass(c, rounds + base, scalars + base * BLSV_SCALAR_LEN, cnt, us + base * BLSV_U_LEN,
-                      gt + base * out_len, ok + base, st, mk, pass_in);
+                      gt + base * out_len, ok + base, st, mk, pass_in, au.at(base));
     }
     hipError_t wipe = hipMemsetAsync(S, 0, host ? l.secret : l.o_scalars, st);
     const hipError_t wipe_k = mask_wipe(c, mk, cnt, st);

@@ -105,6 +105,35 @@ class TencryptResult:
     cs: list
 
 
+@dataclass
+class TencryptAuthResult:
+    """Outcome of Engine.tlock_encrypt_auth: ok[i] (sealed), us[i] = compress(H3(seed_i, msg_i) G1), vs[i] the 32
+    masked seed bytes, ws[i] the masked message; all three None for a refused item (a derived scalar == 0 mod r)."""
+    ok: list
+    us: list
+    vs: list
+    ws: list
+
+
+@dataclass
+class TdecryptAuthResult:
+    """Outcome of Engine.tlock_decrypt_auth: ok[i] (the item decoded AND passed its re-encryption check), reject
+    classes (REJ_*; REJ_TLOCK_AUTH for a failed check), msgs[i] = the message, or None where ok[i] is False."""
+    ok: list
+    reject_class: list
+    msgs: list
+
+
+@dataclass
+class TdecryptAuthRoundsResult:
+    """Outcome of Engine.tlock_decrypt_auth_rounds: ok, reject_class and msgs per item in packed order (as
+    TdecryptAuthResult's), sig_class[j] per round signature (0 = decoded)."""
+    ok: list
+    reject_class: list
+    msgs: list
+    sig_class: list
+
+
 def _packed(items, what):
     """Messages of one length 1 .. TLOCK_MSG_MAX, packed: (bytes, mlen)."""
     items = [bytes(x) for x in items]
@@ -763,6 +792,141 @@ class Engine:
         messages (mlen bytes each, any alignment) -> d_us, d_cs and d_ok as tlock_encrypt_dev writes them."""
         self._check(self.lib.blsv_tlock_encrypt_rounds_dev(self._h, self._seal_key(pk48), d_rounds, d_scalars, d_msgs,
                                                            int(mlen), n, int(kdf), d_us, d_cs, d_ok, stream))
+
+    # ------------------------------------------------------------------ authenticated timelock
+    # include/blsverify.h "authenticated timelock": the Fujisaki-Okamoto transform over the passes above. A
+    # ciphertext is (U, V, W); the sealing scalar is H3(seed, msg); a decrypt reports per item whether the
+    # ciphertext opened (REJ_TLOCK_AUTH otherwise). The project's own instantiation: not kyber's, not tlock's.
+    @staticmethod
+    def _rows(items, size, what):
+        items = [bytes(x) for x in items]
+        if any(len(x) != size for x in items):
+            raise ValueError("%s are %d bytes" % (what, size))
+        return items
+
+    def _encrypt_auth_result(self, n, mlen, us, vs, ws, ok):
+        ub, vb, wb = bytes(us), bytes(vs), bytes(ws)
+        oks = [bool(x) for x in list(ok)[:n]]
+        return TencryptAuthResult(oks, [ub[48 * i:48 * i + 48] if oks[i] else None for i in range(n)],
+                                  [vb[32 * i:32 * i + 32] if oks[i] else None for i in range(n)],
+                                  [wb[mlen * i:mlen * i + mlen] if oks[i] else None for i in range(n)])
+
+    def tlock_encrypt_auth(self, round_, seeds, msgs, pk48=None, kdf=_lib.KDF_SHA256_CTR):
+        """blsv_tlock_encrypt_auth: TencryptAuthResult(ok, us, vs, ws), message i (one length per call, 1 .. 256
+        bytes) locked to `round_` under pk48 (None = the group key) with the 32-byte seed seeds[i], which the
+        CALLER draws fresh and at random per item (callers.timelock_encrypt_auth does)."""
+        sd = self._rows(seeds, _lib.SEED_LEN, "seeds")
+        n = len(sd)
+        mb, mlen = _packed(msgs, "messages")
+        if len(mb) != n * mlen:
+            raise ValueError("one message per seed")
+        us, vs, ws, ok = _lib.out_buf(n * 48), _lib.out_buf(n * 32), _lib.out_buf(n * mlen), _lib.out_buf(n)
+        self._check(self.lib.blsv_tlock_encrypt_auth(self._h, self._seal_key(pk48), int(round_), _lib.buf(b"".join(sd)),
+                                                     _lib.buf(mb), mlen, n, int(kdf), us, vs, ws, ok))
+        return self._encrypt_auth_result(n, mlen, us, vs, ws, ok)
+
+    def tlock_encrypt_auth_dev(self, round_, d_seeds, d_msgs, mlen, n, d_us, d_vs, d_ws, d_ok, pk48=None, stream=None,
+                               kdf=_lib.KDF_SHA256_CTR):
+        """blsv_tlock_encrypt_auth_dev: n device-resident seeds (32 bytes each) and messages (mlen bytes each, any
+        alignment) -> n x 48 bytes at d_us, n x 32 at d_vs, n x mlen at d_ws (d_ws == d_msgs is allowed) and n ok
+        bytes at d_ok; asynchronous on `stream` except for the build of a (key, round) that is not the cached one."""
+        self._check(self.lib.blsv_tlock_encrypt_auth_dev(self._h, self._seal_key(pk48), int(round_), d_seeds, d_msgs,
+                                                         int(mlen), n, int(kdf), d_us, d_vs, d_ws, d_ok, stream))
+
+    def tlock_encrypt_auth_rounds(self, rounds, seeds, msgs, pk48=None, kdf=_lib.KDF_SHA256_CTR):
+        """blsv_tlock_encrypt_auth_rounds: TencryptAuthResult, message i locked to rounds[i] (any uint64) with
+        seeds[i]; the outputs are those of tlock_encrypt_auth(rounds[i], [seeds[i]], [msgs[i]])."""
+        rounds = [int(r) for r in rounds]
+        sd = self._rows(seeds, _lib.SEED_LEN, "seeds")
+        n = len(sd)
+        if len(rounds) != n:
+            raise ValueError("%d rounds for %d seeds" % (len(rounds), n))
+        if any(not 0 <= r < 1 << 64 for r in rounds):
+            raise ValueError("a round is a uint64")
+        mb, mlen = _packed(msgs, "messages")
+        if len(mb) != n * mlen:
+            raise ValueError("one message per seed")
+        us, vs, ws, ok = _lib.out_buf(n * 48), _lib.out_buf(n * 32), _lib.out_buf(n * mlen), _lib.out_buf(n)
+        self._check(self.lib.blsv_tlock_encrypt_auth_rounds(self._h, self._seal_key(pk48),
+                                                            (ctypes.c_uint64 * max(n, 1))(*rounds), _lib.buf(b"".join(sd)),
+                                                            _lib.buf(mb), mlen, n, int(kdf), us, vs, ws, ok))
+        return self._encrypt_auth_result(n, mlen, us, vs, ws, ok)
+
+    def tlock_encrypt_auth_rounds_dev(self, d_rounds, d_seeds, d_msgs, mlen, n, d_us, d_vs, d_ws, d_ok, pk48=None,
+                                      stream=None, kdf=_lib.KDF_SHA256_CTR):
+        """blsv_tlock_encrypt_auth_rounds_dev: n device-resident rounds (uint64 each, 8-byte aligned), seeds and
+        messages -> d_us, d_vs, d_ws and d_ok as tlock_encrypt_auth_dev writes them."""
+        self._check(self.lib.blsv_tlock_encrypt_auth_rounds_dev(self._h, self._seal_key(pk48), d_rounds, d_seeds, d_msgs,
+                                                                int(mlen), n, int(kdf), d_us, d_vs, d_ws, d_ok, stream))
+
+    def tlock_decrypt_auth(self, sig, us, vs, ws, kdf=_lib.KDF_SHA256_CTR):
+        """blsv_tlock_decrypt_auth: TdecryptAuthResult(ok, reject_class, msgs) over the ciphertexts (us[i], vs[i],
+        ws[i]) under the 96-byte round signature `sig`; every ws[i] has the same length, 1 .. 256 bytes. msgs[i]
+        is the message where the item decoded and passed its check, else None (REJ_TLOCK_AUTH, or U's decode
+        class). Raises SignatureRejected as tlock_open does for a signature that does not decode. No beacon
+        verification is needed beside it: under a signature of another round every item is REJ_TLOCK_AUTH."""
+        sig = bytes(sig)
+        if len(sig) != 96:
+            raise ValueError("the round signature is 96 bytes")
+        us = self._rows(us, 48, "U values")
+        vs = self._rows(vs, _lib.V_LEN, "V values")
+        n = len(us)
+        wb, mlen = _packed(ws, "ciphertexts")
+        if len(wb) != n * mlen or len(vs) != n:
+            raise ValueError("one V and one W per U value")
+        out, ok, cls = _lib.out_buf(n * mlen), _lib.out_buf(n), _lib.out_buf(n)
+        sc = ctypes.c_uint8()
+        rc = self.lib.blsv_tlock_decrypt_auth(self._h, _lib.buf(sig), _lib.buf(b"".join(us)), _lib.buf(b"".join(vs)),
+                                              _lib.buf(wb), mlen, n, int(kdf), out, ok, cls,
+                                              ctypes.cast(ctypes.byref(sc), u8p))
+        if rc == _lib.BLSV_EINVAL and sc.value:
+            raise SignatureRejected(rc, self.lib.blsv_last_error(self._h).decode(), sc.value)
+        self._check(rc)
+        ob = bytes(out)
+        oks = [bool(x) for x in list(ok)[:n]]
+        return TdecryptAuthResult(oks, list(cls)[:n], [ob[mlen * i:mlen * i + mlen] if oks[i] else None for i in range(n)])
+
+    def tlock_decrypt_auth_dev(self, sig, d_us, d_vs, d_ws, mlen, n, d_out, d_cls, stream=None, kdf=_lib.KDF_SHA256_CTR):
+        """blsv_tlock_decrypt_auth_dev: n device-resident ciphertexts -> n x mlen bytes at d_out (d_out == d_ws is
+        allowed; zeros for an item that is not good) and the class bytes at d_cls, which is REQUIRED; asynchronous
+        on `stream` except for the read-back of a new signature's decode class."""
+        sig = bytes(sig)
+        if len(sig) != 96:
+            raise ValueError("the round signature is 96 bytes")
+        self._check(self.lib.blsv_tlock_decrypt_auth_dev(self._h, _lib.buf(sig), d_us, d_vs, d_ws, int(mlen), n, int(kdf),
+                                                         d_out, d_cls, stream))
+
+    def tlock_decrypt_auth_rounds(self, sigs, us_per_round, vs_per_round, ws_per_round, kdf=_lib.KDF_SHA256_CTR):
+        """blsv_tlock_decrypt_auth_rounds: as tlock_decrypt_rounds takes `sigs` and `us_per_round`, with round j's V
+        and W values in vs_per_round[j] / ws_per_round[j] (one W length for the whole call). Returns
+        TdecryptAuthRoundsResult(ok, reject_class, msgs, sig_class) in packed order."""
+        runs = [self._rows(run, 48, "U values") for run in us_per_round]
+        vruns = [self._rows(run, _lib.V_LEN, "V values") for run in vs_per_round]
+        wruns = [list(run) for run in ws_per_round]
+        if [len(r) for r in vruns] != [len(r) for r in runs] or [len(r) for r in wruns] != [len(r) for r in runs]:
+            raise ValueError("one V and one W per U value, round by round")
+        us = [u for run in runs for u in run]
+        sb, counts, m = self._rounds_args(sigs, [len(run) for run in runs])
+        n = len(us)
+        wb, mlen = _packed([w for run in wruns for w in run], "ciphertexts")
+        out, ok, cls, sc = _lib.out_buf(n * mlen), _lib.out_buf(n), _lib.out_buf(n), _lib.out_buf(m)
+        self._check(self.lib.blsv_tlock_decrypt_auth_rounds(self._h, sb, counts, m, _lib.buf(b"".join(us)),
+                                                            _lib.buf(b"".join(v for run in vruns for v in run)),
+                                                            _lib.buf(wb), mlen, n, int(kdf), out, ok, cls, sc))
+        ob = bytes(out)
+        oks = [bool(x) for x in list(ok)[:n]]
+        return TdecryptAuthRoundsResult(oks, list(cls)[:n],
+                                        [ob[mlen * i:mlen * i + mlen] if oks[i] else None for i in range(n)],
+                                        list(sc)[:m])
+
+    def tlock_decrypt_auth_rounds_dev(self, sigs, counts, d_us, d_vs, d_ws, mlen, n, d_out, d_cls, d_sig_cls=None,
+                                      stream=None, kdf=_lib.KDF_SHA256_CTR):
+        """blsv_tlock_decrypt_auth_rounds_dev: `sigs` and `counts` on the host over n device-resident ciphertexts
+        -> n x mlen bytes at d_out, the class bytes at d_cls (REQUIRED, n) and optionally d_sig_cls (m);
+        asynchronous on `stream`, no class is read back."""
+        sb, cn, m = self._rounds_args(sigs, counts)
+        self._check(self.lib.blsv_tlock_decrypt_auth_rounds_dev(self._h, sb, cn, m, d_us, d_vs, d_ws, int(mlen), n,
+                                                                int(kdf), d_out, d_cls, d_sig_cls, stream))
 
     # ------------------------------------------------------------------ stage profiling
     STAGES = ("hash", "decompress", "miller", "final_exp", "finish", "lat", "rlc", "tlock")

@@ -679,7 +679,8 @@ int blsv_tseal_lat_stats(blsv_ctx* ctx, uint64_t* launches, uint64_t* items);
  * reject_class, sig_class, BLSV_REJ_TLOCK_SIG, BLSV_EINVAL with *sig_class set and no per-item output touched
  * for a sigma that does not decode, BLSV_ENOGROUP, the refusal of k == 0 (mod r), the caches, and the
  * counters: each entry point counts in the *_stats of the pass it runs. As there, nothing checks that
- * sigma is the round's signature: a wrong one decrypts to garbage without any error.
+ * sigma is the round's signature: a wrong one decrypts to garbage without any error (the authenticated forms
+ * below, blsv_tlock_decrypt_auth*, do report it).
  *
  * Host forms: a pass uploads its cnt x mlen input bytes beside what it uploads today and downloads cnt x mlen
  * output bytes and the class bytes; the staging is the pipeline's (memory contract above, unchanged).
@@ -730,6 +731,94 @@ int blsv_tlock_encrypt_rounds(blsv_ctx* ctx, const uint8_t* pk48, const uint64_t
 int blsv_tlock_encrypt_rounds_dev(blsv_ctx* ctx, const uint8_t* pk48, const uint64_t* d_rounds,
                                   const uint8_t* d_scalars32, const uint8_t* d_msgs, size_t mlen, size_t n, int kdf,
                                   uint8_t* d_out_us48, uint8_t* d_out_cs, uint8_t* d_ok, void* stream);
+
+/*
+ * Authenticated timelock: ciphertexts that report whether they opened. The scheme above cannot tell its
+ * caller that a decryption failed: a ciphertext whose U or masked bytes were altered, one opened with the
+ * wrong round's signature and one sealed under another key all come back as ok = 1 with plausible bytes. The
+ * eight entry points below apply the Fujisaki-Okamoto transform (Boneh-Franklin "FullIdent"): the sealing
+ * scalar is not drawn but derived from a random seed and the message, and the opener re-derives it and checks
+ * that it reproduces U. A decrypt needs no separate beacon verification: under a wrong signature every item
+ * fails its check.
+ *
+ * THIS INSTANTIATION IS THE PROJECT'S OWN, as BLSV_KDF_SHA256_CTR is: SHA-256 with this project's tags over
+ * this project's Gt encoding. kyber's IBE hashes are BLAKE2-based and its Gt encoding is not pinned here. IT
+ * IS NOT WIRE-COMPATIBLE WITH kyber OR tlock: neither opens the other's ciphertexts.
+ *
+ * The scheme. TAG3 = "BLSV-TLOCK-FO-H3", TAG4 = "BLSV-TLOCK-FO-H4" (16 ASCII bytes each). A ciphertext of an
+ * mlen-byte message M is (U: BLSV_U_LEN bytes, V: BLSV_V_LEN bytes, W: mlen bytes); mlen follows
+ * blsv_tlock_encrypt's rules (1 .. BLSV_TLOCK_MSG_MAX, uniform per call, packed, no alignment asked for) and
+ * kdf must be BLSV_KDF_SHA256_CTR (anything else: BLSV_EINVAL, nothing touched).
+ *     H3(s, M)    = (SHA-256(TAG3 || s || M || BE32(0)) || first 16 bytes of SHA-256(TAG3 || s || M || BE32(1)))
+ *                   read as a 384-bit big-endian integer, mod r
+ *     H2(G)       = SHA-256(G || BE32(0)) over the BLSV_GT_LEN-byte encoding: block 0 of BLSV_KDF_SHA256_CTR
+ *     H4(s, mlen) = SHA-256(TAG4 || s || BE32(0)) || SHA-256(TAG4 || s || BE32(1)) || ...  truncated to mlen
+ * Encrypt(pk, round, seed s, M): k = H3(s, M); U = compress(k G1); K = e(pk, H(MessageV2(round)))^(3k),
+ * exactly the K of blsv_tlock_seal / _seal_rounds for the scalar k; V = s XOR H2(encode(K)); W = M XOR H4(s, mlen).
+ * THE CALLER DRAWS THE SEEDS, BLSV_SEED_LEN fresh random bytes per item; the engine draws nothing. A seed
+ * alone unmasks its message. If k == 0 (mod r) the item is refused as a zero scalar is: ok = 0 and U, V and W
+ * all zeros (no SHA-256 input is known to reach this).
+ * Decrypt(sigma, U, V, W): E = e(U, sigma)^3 as blsv_tlock_open computes it; s' = V XOR H2(encode(E));
+ * M' = W XOR H4(s', mlen); k' = H3(s', M'). The item is good iff k' != 0 and k' G1 is the decoded U. A good
+ * item gets ok = 1, class 0 and M'. Any other gets ok = 0, BLSV_REJ_TLOCK_AUTH and mlen zero bytes; its
+ * neighbours are unaffected, and its candidate plaintext is never stored to memory (the check runs first).
+ * Class precedence: a U that does not decode keeps its class 2..6; an item under a sigma that does not decode
+ * keeps BLSV_REJ_TLOCK_SIG (rounds forms), or the call returns BLSV_EINVAL with *sig_class set (one-sigma
+ * forms), exactly as the matching blsv_tlock_decrypt* does; BLSV_REJ_TLOCK_AUTH comes last. U at infinity and
+ * sigma at infinity are no longer "a value like any other": E = 1 is a key everyone knows and no k' != 0 maps
+ * to infinity, so both are BLSV_REJ_TLOCK_AUTH.
+ *
+ * Everything else is the matching entry point's -- blsv_tlock_encrypt for blsv_tlock_encrypt_auth, and so on:
+ * the argument rules, BLSV_EINVAL / BLSV_ENOGROUP with nothing touched, chunked passes with identical outputs,
+ * the caches, and the counters (a call counts in the *_stats of the pass it runs). In place is allowed:
+ * out_msgs == ws and out_ws == msgs. One exception: d_reject_class is REQUIRED in the _decrypt_auth*_dev
+ * forms, because the verdict is the point; NULL with n > 0 is BLSV_EINVAL.
+ *
+ * Staging: one device buffer of the feature's own, below 1 KiB per item of a pass, allocated at the first
+ * authenticated call; a context that only decrypts also builds the 92,160-byte table of G1's multiples the
+ * sealing uses. Secrecy (encrypt): the staged seeds, the derived scalars (the _dev forms stage them too) and
+ * the captured K are cleared on the device behind the kernels that read them, also when a pass fails; the
+ * host forms clear their staged plaintexts too and upload seeds and plaintexts straight from the caller's
+ * memory. No constant-time claim, as above.
+ *
+ * Latency path: the host forms here ALWAYS take the batch path, whatever blsv_set_tlock_lat_max /
+ * blsv_set_tseal_lat_max say. There is no service entry and no multi-context form.
+ *
+ * Measured on one MI355X (profiles/tauth_bench.json; 1 Mi items, mlen = 32, the authenticated
+ * entry and its mirror alternating call by call, medians): blsv_tlock_decrypt_auth_dev 303.0 ms against 291.2 ms
+ * for blsv_tlock_decrypt_dev (+4.05%; 4.2% predicted from the check's 653 Fp products per item),
+ * blsv_tlock_encrypt_auth_dev 85.0 against 84.5 ms for blsv_tlock_encrypt_dev.
+ */
+#define BLSV_SEED_LEN 32
+#define BLSV_V_LEN 32
+#define BLSV_REJ_TLOCK_AUTH 10 /* the item failed the re-encryption check of blsv_tlock_decrypt_auth* */
+int blsv_tlock_encrypt_auth(blsv_ctx* ctx, const uint8_t* pk48, uint64_t round, const uint8_t* seeds32,
+                            const uint8_t* msgs, size_t mlen, size_t n, int kdf, uint8_t* out_us48, uint8_t* out_vs32,
+                            uint8_t* out_ws, uint8_t* ok);
+int blsv_tlock_encrypt_auth_dev(blsv_ctx* ctx, const uint8_t* pk48, uint64_t round, const uint8_t* d_seeds32,
+                                const uint8_t* d_msgs, size_t mlen, size_t n, int kdf, uint8_t* d_out_us48,
+                                uint8_t* d_out_vs32, uint8_t* d_out_ws, uint8_t* d_ok, void* stream);
+int blsv_tlock_encrypt_auth_rounds(blsv_ctx* ctx, const uint8_t* pk48, const uint64_t* rounds, const uint8_t* seeds32,
+                                   const uint8_t* msgs, size_t mlen, size_t n, int kdf, uint8_t* out_us48,
+                                   uint8_t* out_vs32, uint8_t* out_ws, uint8_t* ok);
+int blsv_tlock_encrypt_auth_rounds_dev(blsv_ctx* ctx, const uint8_t* pk48, const uint64_t* d_rounds,
+                                       const uint8_t* d_seeds32, const uint8_t* d_msgs, size_t mlen, size_t n, int kdf,
+                                       uint8_t* d_out_us48, uint8_t* d_out_vs32, uint8_t* d_out_ws, uint8_t* d_ok,
+                                       void* stream);
+int blsv_tlock_decrypt_auth(blsv_ctx* ctx, const uint8_t* sig96, const uint8_t* us48, const uint8_t* vs32,
+                            const uint8_t* ws, size_t mlen, size_t n, int kdf, uint8_t* out_msgs, uint8_t* ok,
+                            uint8_t* reject_class /*optional*/, uint8_t* sig_class /*optional*/);
+int blsv_tlock_decrypt_auth_dev(blsv_ctx* ctx, const uint8_t* sig96, const uint8_t* d_us48, const uint8_t* d_vs32,
+                                const uint8_t* d_ws, size_t mlen, size_t n, int kdf, uint8_t* d_out_msgs,
+                                uint8_t* d_reject_class /*required*/, void* stream);
+int blsv_tlock_decrypt_auth_rounds(blsv_ctx* ctx, const uint8_t* sigs96, const uint64_t* counts, size_t m,
+                                   const uint8_t* us48, const uint8_t* vs32, const uint8_t* ws, size_t mlen, size_t n,
+                                   int kdf, uint8_t* out_msgs, uint8_t* ok, uint8_t* reject_class /*optional, n*/,
+                                   uint8_t* sig_class /*optional, m*/);
+int blsv_tlock_decrypt_auth_rounds_dev(blsv_ctx* ctx, const uint8_t* sigs96, const uint64_t* counts, size_t m,
+                                       const uint8_t* d_us48, const uint8_t* d_vs32, const uint8_t* d_ws, size_t mlen,
+                                       size_t n, int kdf, uint8_t* d_out_msgs, uint8_t* d_reject_class /*required*/,
+                                       uint8_t* d_sig_class /*optional*/, void* stream);
 
 /* ---------------------------------------------------------------- thread-safe service
  *

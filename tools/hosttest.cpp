@@ -370,6 +370,38 @@ int test_hostlogic() {
              std::to_string(l.total) + ", " + std::to_string(l.secret) + "]";
     }
   }
+  out += "]}, \"tauth\": {\"fits\": [";
+  {
+    // blsv_tlock_encrypt_auth* / blsv_tlock_decrypt_auth*: the guard on (kdf, mlen, n) at both sides of its
+    // limits, and the layout of a pass in the feature's own staging
+    const size_t lim = SIZE_MAX / 1024;
+    struct Fit {
+      int kdf;
+      size_t mlen, n;
+    };
+    const Fit fits[10] = {{1, 1, 0},   {1, 256, 1}, {1, 32, lim},     {1, 32, lim + 1}, {1, 0, 1},
+                          {1, 257, 1}, {0, 32, 1},  {2, 32, 1}, {1, 256, SIZE_MAX}, {1, 3, size_t(1) << 20}};
+    for (int k = 0; k < 10; k++) {
+      const bool f = tauth_fits(fits[k].kdf, fits[k].mlen, fits[k].n);
+      if (f) {
+        const TauthLayout l = tauth_layout(fits[k].n, fits[k].mlen);
+        CHECK(l.total >= fits[k].n && l.total <= 1024 * fits[k].n + 16);  // no byte count of the call wraps
+      }
+      out += std::string(k ? ", " : "") + (f ? "true" : "false");
+    }
+    out += "], \"layout\": [";
+    const size_t cases[5][2] = {{1, 1}, {64, 3}, {65, 33}, {16384, 256}, {size_t(1) << 20, 32}};
+    for (int k = 0; k < 5; k++) {
+      const size_t cnt = cases[k][0], mlen = cases[k][1];
+      const TauthLayout l = tauth_layout(cnt, mlen);
+      CHECK(l.o_seeds == 0 && l.o_scalars == 32 * cnt && l.o_in == 64 * cnt && l.secret >= l.o_in + cnt * mlen);
+      CHECK(l.o_rounds == l.secret && l.o_rounds % 8 == 0 && l.o_us == l.o_rounds + 8 * cnt && l.o_vs == l.o_us + 48 * cnt);
+      CHECK(l.o_out == l.o_vs + 32 * cnt && l.o_out % 8 == 0 && l.o_flag >= l.o_out + cnt * mlen && l.o_flag % 8 == 0);
+      CHECK(l.total == l.o_flag + cnt && l.total <= 1024 * cnt);
+      out += std::string(k ? ", " : "") + "[" + std::to_string(l.o_in) + ", " + std::to_string(l.secret) + ", " +
+             std::to_string(l.o_out) + ", " + std::to_string(l.o_flag) + ", " + std::to_string(l.total) + "]";
+    }
+  }
   out += "]}, \"open_rounds\": {\"fits\": [";
   {
     // blsv_tlock_open_rounds*: the guard on (counts, m, n) -- the sum must be n without wrapping, and

@@ -24,6 +24,7 @@
 #include "../drand_amd/csrc/tseal.h"
 #include "../drand_amd/csrc/tsealr.h"
 #include "../drand_amd/csrc/tmask.h"
+#include "../drand_amd/csrc/tauth.h"
 
 namespace bls {
 unsigned long long g_fp_mul_count = 0;
@@ -742,6 +743,191 @@ static int cmd_tmask() {
   return match ? 0 : 1;
 }
 
+// tauth: the authenticated timelock's forms (drand_amd/csrc/tauth.h) as the device runs them. stdin: the first
+// line is mlen (1 .. 256), then one line per case:
+//   reduce <hex96>                           tauth_reduce384 of 48 big-endian bytes
+//   seal <seed32hex> <msghex> <gt576hex>     k = H3, then V and W from the given K (zeros when k == 0)
+//   open <gt576hex> <u48hex> <v32hex> <whex> [class]
+//                                            the opening tail over the given E; u48 is decoded here, an
+//                                            undecodable one gives its class, a class other than 0 is kept
+// The seal cases run as one packed batch and so do the open cases, each with guard bytes around every
+// output. "forms_match": the byte stores, the dword stores (mlen a multiple of 4) and the in-place run all
+// give the same bytes, classes and scalars, and every guard is intact. "fp_mul_open": the Fp products of the
+// last good item's check (the T1 walk and the comparison).
+static int cmd_tauth() {
+  static char buf[8192];
+  if (!fgets(buf, sizeof buf, stdin)) return 2;
+  const unsigned long mlen = strtoul(buf, nullptr, 10);
+  if (mlen < 1 || mlen > (unsigned long)TMASK_MSG_MAX) return 2;
+  struct SealIn {
+    std::vector<uint8_t> seed, msg, gt;
+  };
+  struct OpenIn {
+    std::vector<uint8_t> gt, u, v, w;
+    int cls;
+  };
+  std::vector<std::vector<uint8_t>> reds;
+  std::vector<SealIn> seals;
+  std::vector<OpenIn> opens;
+  while (fgets(buf, sizeof buf, stdin)) {
+    char* save = nullptr;
+    const char* cmd = strtok_r(buf, " \n", &save);
+    if (!cmd) continue;
+    std::vector<const char*> a;
+    while (const char* t = strtok_r(nullptr, " \n", &save)) a.push_back(t);
+    if (!strcmp(cmd, "reduce") && a.size() == 1) {
+      reds.push_back(unhex(a[0]));
+      if (reds.back().size() != 48) return 2;
+    } else if (!strcmp(cmd, "seal") && a.size() == 3) {
+      seals.push_back({unhex(a[0]), unhex(a[1]), unhex(a[2])});
+      const SealIn& x = seals.back();
+      if (x.seed.size() != 32 || x.msg.size() != mlen || x.gt.size() != (size_t)TMASK_GT_LEN) return 2;
+    } else if (!strcmp(cmd, "open") && (a.size() == 4 || a.size() == 5)) {
+      opens.push_back({unhex(a[0]), unhex(a[1]), unhex(a[2]), unhex(a[3]), a.size() == 5 ? atoi(a[4]) : 0});
+      const OpenIn& x = opens.back();
+      if (x.gt.size() != (size_t)TMASK_GT_LEN || x.u.size() != 48 || x.v.size() != 32 || x.w.size() != mlen) return 2;
+    } else {
+      return 2;
+    }
+  }
+  constexpr size_t G = 8;  // guard bytes (a multiple of 4: the dword runs stay aligned)
+  auto guarded = [&](std::vector<uint32_t>& back, size_t bytes) {
+    back.assign((2 * G + bytes) / 4 + 2, 0);
+    memset(back.data(), 0xAA, 2 * G + bytes);
+    return (uint8_t*)back.data() + G;
+  };
+  auto guards_ok = [&](const uint8_t* p, size_t bytes) {
+    for (size_t g = 0; g < G; g++)
+      if ((p - G)[g] != 0xAA || p[bytes + g] != 0xAA) return false;
+    return true;
+  };
+  auto gt_mid = [&](const std::vector<uint8_t>& gt, uint32_t (&mid)[8]) {
+    std::vector<uint32_t> E(144);
+    for (int k = 0; k < 12; k++) st_fp(E.data(), 1, 0, 11 - k, fp_to_mont(fp_raw_from_be48(gt.data() + 48 * k)));
+    tmask_midstate(mid, [&](int k) { return tmask_coef_soa(E.data(), 1, 0, k); });
+  };
+  bool match = true;
+
+  printf("{\"mlen\": %lu, \"reduce\": [", mlen);
+  for (size_t i = 0; i < reds.size(); i++) {
+    uint32_t be[12], k[8];
+    for (int w = 0; w < 12; w++) be[w] = load_be32(reds[i].data() + 4 * w);
+    const bool nz = tauth_reduce384(be, k);
+    uint8_t kb[32];
+    tauth_scalar_bytes(kb, k);
+    printf("%s{\"k\": \"%s\", \"nonzero\": %s}", i ? ", " : "", hex_of(kb, 32).c_str(), nz ? "true" : "false");
+  }
+
+  // ---- the sealing side: derive, then the tail from the given K
+  struct SealOut {
+    std::vector<uint8_t> k, v, w;
+    std::vector<int> ok;
+    bool operator==(const SealOut& o) const { return k == o.k && v == o.v && w == o.w && ok == o.ok; }
+  };
+  const size_t ns = seals.size();
+  auto run_seal = [&](bool words, bool in_place) {
+    SealOut o;
+    std::vector<uint32_t> bv, bw, bm;
+    uint8_t* V = guarded(bv, 32 * ns);
+    uint8_t* W = guarded(bw, mlen * ns);
+    bm.assign(mlen * ns / 4 + 2, 0);
+    uint8_t* M = in_place ? W : (uint8_t*)bm.data();
+    for (size_t i = 0; i < ns; i++) memcpy(M + i * mlen, seals[i].msg.data(), mlen);
+    o.k.resize(32 * ns);
+    for (size_t i = 0; i < ns; i++) {
+      uint32_t seed[8], k[8], mid[8] = {0};
+      tauth_seed_words(seed, seals[i].seed.data());
+      bool sealed = words ? tauth_derive<true>(seed, M + i * mlen, (uint32_t)mlen, k)
+                          : tauth_derive<false>(seed, M + i * mlen, (uint32_t)mlen, k);
+      tauth_scalar_bytes(o.k.data() + 32 * i, k);
+      uint32_t k2[8];
+      sealed = tseal_scalar(o.k.data() + 32 * i, k2);  // what k_tseal_u reads back from the staging row
+      for (int w = 0; w < 8; w++) match &= k2[w] == k[w];
+      o.ok.push_back(sealed);
+      if (sealed) gt_mid(seals[i].gt, mid);
+      if (words)
+        tauth_seal_tail<true>(mid, sealed, seed, M + i * mlen, (uint32_t)mlen, V + 32 * i, W + i * mlen);
+      else
+        tauth_seal_tail<false>(mid, sealed, seed, M + i * mlen, (uint32_t)mlen, V + 32 * i, W + i * mlen);
+    }
+    if (!guards_ok(V, 32 * ns) || !guards_ok(W, mlen * ns)) match = false;
+    o.v.assign(V, V + 32 * ns);
+    o.w.assign(W, W + mlen * ns);
+    return o;
+  };
+  printf("], \"seal\": [");
+  if (ns) {
+    const SealOut o = run_seal(false, false);
+    match &= run_seal(false, true) == o;
+    if (mlen % 4 == 0) match &= run_seal(true, false) == o && run_seal(true, true) == o;
+    for (size_t i = 0; i < ns; i++)
+      printf("%s{\"k\": \"%s\", \"ok\": %d, \"v\": \"%s\", \"w\": \"%s\"}", i ? ", " : "", hex_of(o.k.data() + 32 * i, 32).c_str(),
+             o.ok[i], hex_of(o.v.data() + 32 * i, 32).c_str(), hex_of(o.w.data() + mlen * i, mlen).c_str());
+  }
+
+  // ---- the opening side
+  static g1a T1[TSEAL_WINDOWS * TSEAL_ENTRIES];
+  const size_t no = opens.size();
+  if (no)
+    for (int w = 0; w < TSEAL_WINDOWS; w++) tseal_g1_row(w, [&](int j, const g1a& p) { T1[tseal_entry(w, j)] = p; });
+  unsigned long long n_check = 0;
+  struct OpenOut {
+    std::vector<uint8_t> msg, cls;
+    bool operator==(const OpenOut& o) const { return msg == o.msg && cls == o.cls; }
+  };
+  auto run_open = [&](bool words, bool in_place) {
+    OpenOut o;
+    std::vector<uint32_t> bo, bw, bv;
+    uint8_t* out = guarded(bo, mlen * no);
+    bw.assign(mlen * no / 4 + 2, 0);
+    bv.assign(8 * no + 2, 0);
+    uint8_t* W = in_place ? out : (uint8_t*)bw.data();
+    uint8_t* V = (uint8_t*)bv.data();
+    for (size_t i = 0; i < no; i++) {
+      memcpy(W + i * mlen, opens[i].w.data(), mlen);
+      memcpy(V + 32 * i, opens[i].v.data(), 32);
+    }
+    for (size_t i = 0; i < no; i++) {
+      g1a U;
+      bool uinf = false;
+      uint8_t cls = g1_decompress(opens[i].u.data(), U, uinf);
+      if (cls == REJ_OK && opens[i].cls) cls = (uint8_t)opens[i].cls;
+      if (cls != REJ_OK) {
+        const uint32_t zero[8] = {0};
+        for (uint32_t j = 0; 32 * j < mlen; j++) {
+          if (words)
+            tauth_store_piece<true>(out + i * mlen, j, tauth_piece_len((uint32_t)mlen, j), zero, true);
+          else
+            tauth_store_piece<false>(out + i * mlen, j, tauth_piece_len((uint32_t)mlen, j), zero, true);
+        }
+      } else {
+        uint32_t mid[8];
+        gt_mid(opens[i].gt, mid);
+        const unsigned long long c0 = g_fp_mul_count;
+        auto entry = [&](int w, int j) { return T1[tseal_entry(w, j)]; };
+        auto ucoord = [&](int c) { return c ? U.y : U.x; };
+        cls = words ? tauth_open_tail<true>(mid, V + 32 * i, W + i * mlen, (uint32_t)mlen, ucoord, uinf, entry, out + i * mlen)
+                    : tauth_open_tail<false>(mid, V + 32 * i, W + i * mlen, (uint32_t)mlen, ucoord, uinf, entry, out + i * mlen);
+        if (cls == REJ_OK) n_check = g_fp_mul_count - c0;
+      }
+      o.cls.push_back(cls);
+    }
+    if (!guards_ok(out, mlen * no)) match = false;
+    o.msg.assign(out, out + mlen * no);
+    return o;
+  };
+  printf("], \"open\": [");
+  if (no) {
+    const OpenOut o = run_open(false, false);
+    match &= run_open(false, true) == o;
+    if (mlen % 4 == 0) match &= run_open(true, false) == o && run_open(true, true) == o;
+    for (size_t i = 0; i < no; i++)
+      printf("%s{\"cls\": %d, \"msg\": \"%s\"}", i ? ", " : "", (int)o.cls[i], hex_of(o.msg.data() + mlen * i, mlen).c_str());
+  }
+  printf("], \"fp_mul_open\": %llu, \"forms_match\": %s}\n", n_check, match ? "true" : "false");
+  return match ? 0 : 1;
+}
+
 // tseal <pk48hex> <round>: the timelock sealing (drand_amd/csrc/tseal.h) as the device runs it -- the base
 // B = e(pk, H(MessageV2(round)))^3 through the opening's own forms (hash, prepared line table, f pass,
 // final exponentiation), the tables T1 (multiples of G1) and T2 (powers of B), then per scalar (stdin, 32
@@ -1166,6 +1352,7 @@ int main(int argc, char** argv) {
   if (argc == 2 && !strcmp(argv[1], "subgroup")) return cmd_subgroup();
   if (argc == 3 && !strcmp(argv[1], "tlock")) return cmd_tlock(argv[2]);
   if (argc == 2 && !strcmp(argv[1], "tmask")) return cmd_tmask();
+  if (argc == 2 && !strcmp(argv[1], "tauth")) return cmd_tauth();
   if (argc == 4 && !strcmp(argv[1], "tseal")) return cmd_tseal(argv[2], strtoull(argv[3], nullptr, 10));
   if (argc == 3 && !strcmp(argv[1], "tsealr")) return cmd_tsealr(argv[2]);
   if (argc >= 4 && !strcmp(argv[1], "tlockr")) return cmd_tlockr(argc - 2, argv + 2);
