@@ -128,6 +128,9 @@ SIGNATURES = {
     "blsv_tlock_lat_stats": (ctypes.c_int, [vp, u64p, u64p]),
     "blsv_set_tseal_lat_max": (sz, [vp, sz]),
     "blsv_tseal_lat_stats": (ctypes.c_int, [vp, u64p, u64p]),
+    "blsv_set_tauth_lat_max": (sz, [vp, sz, sz]),
+    "blsv_tauth_lat_stats": (ctypes.c_int, [vp, u64p, u64p, u64p, u64p]),
+    "blsv_test_tauth_walk_waves": (ctypes.c_int, [vp, ctypes.c_int]),
     "blsv_tlock_seal": (ctypes.c_int, [vp, u8p, ctypes.c_uint64, u8p, sz, u8p, u8p, u8p]),
     "blsv_tlock_seal_dev": (ctypes.c_int, [vp, u8p, ctypes.c_uint64, vp, sz, vp, vp, vp, vp]),
     "blsv_tlock_seal_stats": (ctypes.c_int, [vp, u64p, u64p]),

@@ -41,6 +41,8 @@ int ensure_workspace(blsv_ctx* c, size_t cnt) {
     c->lat_max = std::min(c->lat_max, c->chunk);
     c->tlock_lat.lat_max = std::min(c->tlock_lat.lat_max, c->chunk);
     c->tseal_lat.lat_max = std::min(c->tseal_lat.lat_max, c->chunk);
+    c->tauth_lat.open_max = std::min(c->tauth_lat.open_max, c->chunk);
+    c->tauth_lat.seal_max = std::min(c->tauth_lat.seal_max, c->chunk);
     c->oom_halvings++;
   }
 }
@@ -120,6 +122,8 @@ int blsv_create(int device, blsv_ctx** out) {
   c->device = device;
   c->tlock_lat.lat_max = std::min(tlock_lat_max_env(), c->chunk);
   c->tseal_lat.lat_max = std::min(tseal_lat_max_env(), c->chunk);
+  c->tauth_lat.open_max = std::min(tauth_lat_max_env("BLSV_TAUTH_OPEN_LAT_MAX"), c->chunk);
+  c->tauth_lat.seal_max = std::min(tauth_lat_max_env("BLSV_TAUTH_SEAL_LAT_MAX"), c->chunk);
   hipError_t e = hipSetDevice(device);
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking);
@@ -243,6 +247,25 @@ int blsv_tseal_lat_stats(blsv_ctx* c, uint64_t* launches, uint64_t* items) {
   return BLSV_OK;
 }
 
+// cutovers of the authenticated timelock's latency path (include/blsverify.h "authenticated timelock"; 0 =
+// off, SIZE_MAX = keep); returns the larger of the two values in force
+size_t blsv_set_tauth_lat_max(blsv_ctx* c, size_t open_items, size_t seal_items) {
+  if (!c) return 0;
+  if (open_items != SIZE_MAX) c->tauth_lat.open_max = std::min(open_items, c->chunk);
+  if (seal_items != SIZE_MAX) c->tauth_lat.seal_max = std::min(seal_items, c->chunk);
+  return std::max(c->tauth_lat.open_max, c->tauth_lat.seal_max);
+}
+
+int blsv_tauth_lat_stats(blsv_ctx* c, uint64_t* open_launches, uint64_t* open_items, uint64_t* seal_launches,
+                         uint64_t* seal_items) {
+  if (!c) return BLSV_EINVAL;
+  if (open_launches) *open_launches = c->tauth_lat.open_launches;
+  if (open_items) *open_items = c->tauth_lat.open_items;
+  if (seal_launches) *seal_launches = c->tauth_lat.seal_launches;
+  if (seal_items) *seal_items = c->tauth_lat.seal_items;
+  return BLSV_OK;
+}
+
 // per-context pass size (include/blsverify.h memory contract)
 size_t blsv_set_chunk(blsv_ctx* c, size_t items) {
   if (!c) return 0;
@@ -259,6 +282,8 @@ size_t blsv_set_chunk(blsv_ctx* c, size_t items) {
   c->lat_max = std::min(c->lat_max, v);
   c->tlock_lat.lat_max = std::min(c->tlock_lat.lat_max, v);
   c->tseal_lat.lat_max = std::min(c->tseal_lat.lat_max, v);
+  c->tauth_lat.open_max = std::min(c->tauth_lat.open_max, v);
+  c->tauth_lat.seal_max = std::min(c->tauth_lat.seal_max, v);
   return prev;
 }
 

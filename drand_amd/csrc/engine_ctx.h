@@ -335,6 +335,21 @@ inline size_t tseal_lat_max_env() {
   return v;
 }
 
+// Cutovers of the authenticated timelock's latency path (blsv_set_tauth_lat_max): BLSV_TAUTH_OPEN_LAT_MAX /
+// BLSV_TAUTH_SEAL_LAT_MAX, parsed as BLSV_TSEAL_LAT_MAX is, else 0 = off. Read once per context.
+inline size_t tauth_lat_max_env(const char* name) {
+  const char* e = getenv(name);
+  if (!e) return 0;
+  char* end = nullptr;
+  errno = 0;
+  const unsigned long long x = strtoull(e, &end, 10);
+  if (end == e || *end != '\0' || errno == ERANGE || e[0] == '-') {
+    fprintf(stderr, "blsverify: ignoring %s=\"%s\" (not a non-negative integer); it stays 0\n", name, e);
+    return 0;
+  }
+  return (size_t)std::min<unsigned long long>(x, kMaxChunk);
+}
+
 struct rlc_state {
   size_t group = kRlcGroupDefault;
   bool seed_pinned = false;  // blsv_test_rlc_seed
@@ -414,6 +429,21 @@ struct tauth_state {
   DBuf buf;
 };
 
+// Authenticated timelock on the latency path (blsv_set_tauth_lat_max, k_lat_tauth_open.hip /
+// k_lat_tauth_seal.hip): host calls of up to open_max (decrypting) or seal_max (encrypting) items, one
+// workgroup per item. Switches, device buffer (hostlogic.h tauth_lat_open_layout / tauth_lat_seal_layout),
+// host staging and counters of its own: the other latency switches are not consulted, and the batch paths'
+// counters, the sigma cache and the (key, round) base cache stay as they are. It reads T1 (tseal_state) and,
+// encrypting, the key table TK through the key cache (tsealr_state), as tseal_lat_state does.
+struct tauth_lat_state {
+  size_t open_max = 0, seal_max = 0;  // never above the chunk
+  uint64_t open_launches = 0, open_items = 0, seal_launches = 0, seal_items = 0;  // blsv_tauth_lat_stats
+  int walk_waves = 8;  // the waves that share the check's walk: 8, or 1 (blsv_test_tauth_walk_waves)
+  DBuf buf;
+  std::vector<uint8_t> up, down;  // an encrypting call's seeds and plaintexts in `up` are cleared before it returns
+  TlockLatPlan plan;
+};
+
 struct blsv_ctx {
   int device = 0;
   bool prof = false;
@@ -481,6 +511,7 @@ struct blsv_ctx {
   tlockr_state tlockr;
   tlock_lat_state tlock_lat;
   tseal_lat_state tseal_lat;
+  tauth_lat_state tauth_lat;
   tauth_state tauth;
 };
 

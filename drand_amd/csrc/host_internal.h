@@ -242,6 +242,21 @@ int sealr_prepare(blsv_ctx* c, const uint8_t* pk48, size_t n, hipStream_t st);
 int tseal_lat_run(blsv_ctx* c, const uint8_t* pk48, const uint64_t* rounds, uint64_t round, const uint8_t* scalars32,
                   size_t n, uint8_t* out_us48, uint8_t* out, uint8_t* ok, const uint8_t* msgs = nullptr, size_t mlen = 0);
 
+// ---- tauth.cpp: T1, the table of G1's multiples, built once per context by whoever needs it first
+int auth_t1(blsv_ctx* c, hipStream_t st);
+
+// ---- tauth_lat.cpp: a host call of n >= 1 items of the authenticated forms on the latency path (hostlogic.h
+// tauth_lat_routes; blsv_set_tauth_lat_max), after the entry point's own argument checks. Decrypting: the
+// arguments of tlock_lat_run with the items' V and W bytes; o.gt points to the n x mlen message bytes (zeros for
+// an item whose class is not 0), so tlock_lat_copy_out with out_len = mlen hands the items over.
+int tauth_lat_open_run(blsv_ctx* c, const uint8_t* sigs96, size_t m, const uint32_t* sig_of, const uint32_t* idle,
+                       size_t n_idle, const uint8_t* us48, const uint8_t* vs32, const uint8_t* ws, size_t mlen, size_t n,
+                       TlockLatOut& o);
+// Encrypting under the key pk48: item i to rounds[i], or every item to `round` when rounds is null
+int tauth_lat_seal_run(blsv_ctx* c, const uint8_t* pk48, const uint64_t* rounds, uint64_t round, const uint8_t* seeds32,
+                       const uint8_t* msgs, size_t mlen, size_t n, uint8_t* out_us48, uint8_t* out_vs32, uint8_t* out_ws,
+                       uint8_t* ok);
+
 // ---- tseal.cpp: the key a sealing call runs under -- pk48, or the group key (BLSV_ENOGROUP without one)
 int seal_key(blsv_ctx* c, const uint8_t* pk48, const uint8_t** key);
 

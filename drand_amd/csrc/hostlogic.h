@@ -519,5 +519,61 @@ inline bool tseal_lat_layout(size_t n, bool rounds, TsealLatLayout& l, size_t ml
   return true;
 }
 
+// ---------------------------------------------------------------- authenticated timelock on the latency path
+// blsv_set_tauth_lat_max: a host call of 1 .. lat_max items of blsv_tlock_decrypt_auth* / blsv_tlock_encrypt_auth*
+// goes to k_lat_tauth_open / k_lat_tauth_seal, one workgroup per item (the decrypting side has a switch of its
+// own, the encrypting side another). The rounds decrypt also needs tlock_lat_plan's consent (no more than
+// lat_max signatures without items).
+inline bool tauth_lat_routes(size_t n, size_t lat_max) { return n >= 1 && n <= lat_max; }
+// Decrypting: one device buffer per call. What the host uploads in one copy -- the m signatures, the n
+// compressed U, the n V, for a call across rounds sig_of and idle (word arrays: every part before them is a
+// multiple of 4 bytes), then the n x mlen W bytes -- and, 64-byte aligned, what one download brings back: the
+// n x mlen message bytes, the n item classes, the m signature classes.
+struct TauthLatOpenLayout {
+  size_t o_sigs, o_us, o_vs, o_sigof, o_idle, o_ws, in_total, o_out, o_cls, o_sigcls, out_total, total;
+};
+// false when a byte count does not fit size_t or mlen is out of range (l is then untouched). Every signature
+// has an item or is idle, so m <= n + n_idle bounds the signatures.
+inline bool tauth_lat_open_layout(size_t m, size_t n, bool rounds, size_t n_idle, size_t mlen, TauthLatOpenLayout& l) {
+  if (mlen < 1 || mlen > BLSV_TLOCK_MSG_MAX || n_idle > SIZE_MAX - n) return false;
+  const size_t q = n + n_idle;
+  if (m > q || q > (SIZE_MAX - 63) / (96 + 1 + 4 + BLSV_U_LEN + 32 + 4 + 1 + 2 * mlen)) return false;
+  l.o_sigs = 0;
+  l.o_us = 96 * m;
+  l.o_vs = l.o_us + BLSV_U_LEN * n;
+  l.o_sigof = l.o_vs + 32 * n;
+  l.o_idle = l.o_sigof + (rounds ? 4 * n : 0);
+  l.o_ws = l.o_idle + 4 * n_idle;
+  l.in_total = l.o_ws + mlen * n;
+  l.o_out = (l.in_total + 63) & ~size_t(63);
+  l.o_cls = l.o_out + mlen * n;
+  l.o_sigcls = l.o_cls + n;
+  l.out_total = l.o_sigcls + m - l.o_out;
+  l.total = l.o_sigcls + m;
+  return true;
+}
+// Encrypting: what the host uploads in one copy -- for a call with a round per item the n rounds, 8 bytes each,
+// first (the buffer is 8-byte aligned), then the n seeds and the n x mlen plaintext bytes -- and, 64-byte
+// aligned, what one download brings back: the n x 48 U bytes (4-byte aligned), the n V, the n x mlen W bytes,
+// the n ok bytes. [o_seeds, in_total) is what the entry clears behind the kernel, in the device and the host
+// copy. No scalar, no k pk and no K is ever in this buffer.
+struct TauthLatSealLayout {
+  size_t o_rounds, o_seeds, o_msgs, in_total, o_us, o_vs, o_ws, o_ok, out_total, total;
+};
+inline bool tauth_lat_seal_layout(size_t n, bool rounds, size_t mlen, TauthLatSealLayout& l) {
+  if (mlen < 1 || mlen > BLSV_TLOCK_MSG_MAX || n > (SIZE_MAX - 63) / (8 + 32 + BLSV_U_LEN + 32 + 1 + 2 * mlen)) return false;
+  l.o_rounds = 0;
+  l.o_seeds = rounds ? 8 * n : 0;
+  l.o_msgs = l.o_seeds + 32 * n;
+  l.in_total = l.o_msgs + mlen * n;
+  l.o_us = (l.in_total + 63) & ~size_t(63);
+  l.o_vs = l.o_us + BLSV_U_LEN * n;
+  l.o_ws = l.o_vs + 32 * n;
+  l.o_ok = l.o_ws + mlen * n;
+  l.out_total = l.o_ok + n - l.o_us;
+  l.total = l.o_ok + n;
+  return true;
+}
+
 }  // namespace blsv_detail
 #pragma GCC visibility pop

@@ -232,6 +232,22 @@ void launch_decompress_g1(const uint8_t* in, size_t cnt, uint32_t* tab, uint8_t*
 // PubPoly.Eval(idx[i]) over t commits (affine table, none at infinity assumed via inf flags)
 void launch_pubpoly_eval(const uint32_t* commits, const uint8_t* commit_inf, uint32_t t, const uint32_t* idx,
                          size_t cnt, uint32_t* out_tab, uint8_t* out_inf, hipStream_t st);
+// authenticated timelock on the latency path (k_lat_tauth_open.hip, k_lat_tauth_seal.hip): one workgroup per
+// item. Opening: launch_lat_tlock's item shape (sig_of, idle, sig_cls) with the item's V (32 bytes) and W (mlen
+// bytes, 1 .. 256, packed) beside its U; out gets n_items x mlen message bytes (zeros unless cls[i] == 0) -- byte
+// for byte what launch_tauth_open_tail gives behind the batch passes. T1: kTsealT1Words words (launch_tseal_g1_table).
+// walk_waves: the waves that share the check's walk, 8 or 1 (the same bytes either way).
+void launch_lat_tauth_open(const uint8_t* sigs, const uint32_t* sig_of, const uint8_t* us, const uint8_t* vs,
+                           const uint8_t* ws, size_t mlen, size_t n_items, const uint32_t* idle, size_t n_idle,
+                           const uint32_t* T1, uint8_t* out, uint8_t* cls, uint8_t* sig_cls, int walk_waves,
+                           hipStream_t st);
+// Sealing: launch_lat_tseal's item shape with the item's seed (32 bytes) and message (mlen bytes, packed) in the
+// scalar's place; us (4-byte aligned) n x 48, vs n x 32, ws n x mlen, ok n -- byte for byte what launch_tauth_derive,
+// the sealing passes and launch_tauth_seal_tail give. Neither the derived scalar nor K is written anywhere.
+void launch_lat_tauth_seal(const uint32_t* T1, const uint32_t* TK, const uint64_t* rounds, uint64_t round,
+                           const uint8_t* seeds, const uint8_t* msgs, size_t mlen, size_t n, uint8_t* us, uint8_t* vs,
+                           uint8_t* ws, uint8_t* ok, hipStream_t st);
+
 // decode only on the latency engine (k_lat.hip; one two-wave workgroup per signature)
 void launch_lat_decode(const uint8_t* sigs, size_t stride, size_t offset, size_t cnt, uint32_t* S, uint8_t* s_inf,
                        uint8_t* cls, hipStream_t st);

@@ -3,14 +3,16 @@
 // mirror: the same preparation and the same passes (tlock.cpp, tlockr.cpp, tseal.cpp, tsealr.cpp) with the
 // authenticated tail in place of the mask tail, and on the encrypting side k_tauth_derive in front, which
 // turns seeds and messages into the scalars the sealing kernels read. The passes run on device pointers; a
-// host form stages a pass of at most cap items in the feature's own buffer (engine_ctx.h has the plan). Always
-// the batch path: the latency switches are not consulted.
+// host form stages a pass of at most cap items in the feature's own buffer (engine_ctx.h has the plan). The
+// switches of the unauthenticated latency paths (blsv_set_tlock_lat_max, blsv_set_tseal_lat_max) are not
+// consulted; with blsv_set_tauth_lat_max the four host forms hand calls of a few items to the latency path of
+// their own (tauth_lat.cpp). The _dev forms always take the batch path.
 #include "host_internal.h"
 
 static_assert(BLSV_REJ_TLOCK_AUTH == 10 && BLSV_REJ_TLOCK_AUTH == BLSV_REJ_TLOCK_SIG + 1, "the next free class");
 
 // T1, the table of G1's multiples the check walks: the sealing's, built once per context by whoever needs it first
-static int auth_t1(blsv_ctx* c, hipStream_t st) {
+int auth_t1(blsv_ctx* c, hipStream_t st) {
   tseal_state& t = c->tseal;
   HIPCHK(c, t.t1.ensure(blsk::kTsealT1Words * 4));
   if (!t.t1_built) {
@@ -107,6 +109,8 @@ static int encrypt_auth(blsv_ctx* c, const char* what, bool host, const uint8_t*
   const uint8_t* key;
   int rc = seal_key(c, pk48, &key);
   if (rc) return rc;
+  if (host && tauth_lat_routes(n, std::min(c->tauth_lat.seal_max, c->chunk)))
+    return tauth_lat_seal_run(c, key, many ? rounds : nullptr, round, seeds, msgs, mlen, n, us, vs, ws, ok);
   rc = many ? sealr_prepare(c, key, n, st) : seal_prepare(c, key, round, n, st);
   if (rc) return rc;
   if (!n) return BLSV_OK;
@@ -175,6 +179,16 @@ int blsv_tlock_decrypt_auth(blsv_ctx* c, const uint8_t* sig96, const uint8_t* us
     return fail(c, BLSV_EINVAL, "tlock_decrypt_auth: bad arguments");
   (void)hipSetDevice(c->device);
   hipStream_t st = c->stream;
+  if (tauth_lat_routes(n, std::min(c->tauth_lat.open_max, c->chunk))) {
+    TlockLatOut o;
+    const int rl = tauth_lat_open_run(c, sig96, 1, nullptr, nullptr, 0, us48, vs32, ws, mlen, n, o);
+    if (rl) return rl;
+    if (sig_class) *sig_class = o.sig_cls[0];
+    if (o.sig_cls[0] != BLSV_REJ_OK)
+      return fail(c, BLSV_EINVAL, "tlock_decrypt_auth: signature rejected (class %d)", (int)o.sig_cls[0]);
+    tlock_lat_copy_out(o, n, out_msgs, ok, reject_class, mlen);
+    return BLSV_OK;
+  }
   int rc = tlock_prepare_sig(c, sig96, st, sig_class);
   if (rc) return rc;
   if (!n) return BLSV_OK;
@@ -225,6 +239,16 @@ int blsv_tlock_decrypt_auth_rounds(blsv_ctx* c, const uint8_t* sigs96, const uin
   (void)hipSetDevice(c->device);
   hipStream_t st = c->stream;
   int rc;
+  const size_t lat_max = std::min(c->tauth_lat.open_max, c->chunk);
+  if (tauth_lat_routes(n, lat_max) && tlock_lat_plan(counts, m, lat_max, c->tauth_lat.plan)) {
+    const TlockLatPlan& p = c->tauth_lat.plan;
+    TlockLatOut o;
+    rc = tauth_lat_open_run(c, sigs96, m, p.sig_of.data(), p.idle.data(), p.idle.size(), us48, vs32, ws, mlen, n, o);
+    if (rc) return rc;
+    if (sig_class) memcpy(sig_class, o.sig_cls, m);
+    tlock_lat_copy_out(o, n, out_msgs, ok, reject_class, mlen);
+    return BLSV_OK;
+  }
   if ((rc = auth_t1(c, st)) || (rc = ensure_workspace(c, std::max(n, size_t(1))))) return rc;
   uint8_t* d_sc = nullptr;
   if (sig_class && m) {

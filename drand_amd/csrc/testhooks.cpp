@@ -86,6 +86,12 @@ int blsv_test_tail_split(blsv_ctx* c, size_t q) {
   return BLSV_OK;
 }
 
+int blsv_test_tauth_walk_waves(blsv_ctx* c, int waves) {
+  if (!c || (waves != 1 && waves != 8)) return BLSV_EINVAL;
+  c->tauth_lat.walk_waves = waves;
+  return BLSV_OK;
+}
+
 int blsv_test_generic_chains(blsv_ctx* c, int on) {
   if (!c) return BLSV_EINVAL;
   blsk::g_generic_chains_all = on != 0;

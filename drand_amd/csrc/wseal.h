@@ -189,4 +189,61 @@ WVI bool seal_team(const uint8_t* k32, const uint32_t (&b0)[8], const uint32_t* 
   return true;
 }
 
+// seal_team's schedule up to and including the final exponentiation, for an item whose scalar is derived
+// and whose tail is not the encoding (wauth.h). k: the reduced scalar, eight little-endian words below r,
+// k_ok: k != 0, as tseal_scalar or tauth_derive leaves them -- so no k32 in memory is needed; all: the
+// whole-workgroup team, fresh from make_team. U is stored; K is not: SEAL_K leaves it in the slots
+// W_A .. W_A + 5, SEAL_ONE in no slot (the pair is skipped: K = 1), and SEAL_REFUSED (k == 0) returns before
+// anything is stored or synced. seal_team keeps its own text: k_lat_tseal is held to compile to what it
+// compiled to.
+constexpr int SEAL_REFUSED = 0, SEAL_ONE = 1, SEAL_K = 2;
+WVI int seal_team_core(Team& all, const uint32_t (&k)[8], bool k_ok, const uint32_t (&b0)[8], const uint32_t* T1,
+                       const uint32_t* TK, uint32_t* out_u) {
+  const int w = wave_id();
+  if (!k_ok) return SEAL_REFUSED;  // every wave alike: no sync is pending
+  if ((HASH_TEAM >> w) & 1u) {
+    Team th = make_team(HASH_TEAM, CTR_HASH);
+    RingCounts rc;
+    G2J q = g2_infinity();
+    if (w == 0) q = team_hash_to_curve_sum(b0, rc);
+    if (w == 5) {
+      for (int i = 0; i < SSWU_POWS; i++) ring_pow_consume(HASH_RING, bls::EXP_P_MINUS_3_DIV_4, rc);
+      iso_serve();
+    }
+    const G2J h = team_clear_cofactor(th, q);
+    if (w == 0) {
+      const bool fin = !g2_is_inf(h);
+      if (fin) {  // Jacobian (X, Y, Z) -> homogeneous (X Z : Y : Z^3), as verify_team
+        xst(S_HX, dot(h.x, h.z));
+        xst(S_HY, h.y);
+        xst(S_HZ, dot(h.z, sqr2(h.z)));
+      }
+      xst_word(XW_HFIN, fin);
+    }
+  } else if (w == 3) {
+    aff_serve();
+  } else if (w == SEAL_WAVE_U) {
+    g1_compress_store(out_u, seal_walk(T1, k));
+  } else if (w == SEAL_WAVE_P) {
+    F px, py;
+    g2_to_affine(seal_walk(TK, k), px, py);
+    xst(S_PX, dup0(px));
+    xst(S_PY, dup0(py));
+  }
+  team_sync(all);
+  const F px = xld(S_PX), py = xld(S_PY);
+  const bool a0 = xld_word(XW_HFIN) != 0u;
+  team_sync(all);  // every wave holds P: its slots go
+  if (w == SEAL_WAVE_P) {
+    xst(S_PX, zero());
+    xst(S_PY, zero());
+  }
+  if (!a0) return SEAL_ONE;  // not reachable by a test: no message is known to hash to infinity
+  const MPair m0 = mpair_proj(px, py, xld(S_HX), xld(S_HY), xld(S_HZ));
+  const int f = team_miller(all, m0, TB0);
+  team_final_exp(all, f);
+  return SEAL_K;
+}
+
+
 }  // namespace wv

@@ -1011,6 +1011,65 @@ WVI uint8_t tlock_team(const uint8_t* sig, const uint8_t* u48, uint32_t* out, ui
 }
 
 
+// tlock_team's schedule up to and including the final exponentiation, for an item whose tail is not the
+// encoding (wauth.h): nothing is stored to global memory. all: the whole-workgroup team, fresh from
+// make_team. Every wave returns the same class and sets the same sig_cls; for the class 0 the value E is
+// left in the slots W_A .. W_A + 5, or e_one is set and no slot holds it (U or sigma at infinity: the pair
+// is skipped, E = 1). tlock_team keeps its own text: k_lat_tlock is held to compile to what it compiled to.
+WVI uint8_t tlock_team_core(Team& all, const uint8_t* sig, const uint8_t* u48, uint8_t& sig_cls, bool& e_one) {
+  const int w = wave_id();
+  if ((HASH_TEAM >> w) & 1u) {
+    Team th = make_team(HASH_TEAM, CTR_HASH);
+    RingCounts rc;
+    if (w == 0) {
+      F x, y;
+      bool inf;
+      const uint8_t c = g1_decompress(u48, x, y, inf, PowRing{&HASH_RING, &rc}, false);
+      if (c == bls::REJ_OK && !inf) {
+        xst(S_UX, x);
+        xst(S_UY, y);
+      }
+      xst_word(XW_UCLS, c);
+      xst_word(XW_UINF, inf);
+      flag_post(CTR_UDEC);
+    } else if (w == 5) {
+      for (int k = 0; k < G1_DEC_POWS; k++)
+        if (!ring_pow_consume(HASH_RING, bls::EXP_P_MINUS_3_DIV_4, rc, CTR_UDEC)) break;
+    }
+    flag_wait(CTR_UDEC, 1);
+    bool sub_ok = true;
+    if (xld_word(XW_UCLS) == bls::REJ_OK && !xld_word(XW_UINF)) sub_ok = team_g1_in_subgroup(th);
+    if (w == 0) xst_word(XW_USUB, sub_ok);
+  } else if (w == 1) {
+    team_sig_decode(sig, w);
+  } else {
+    Team t1 = make_team(SIG_TEAM, CTR_SIG);
+    team_sig_decode(sig, w);
+    flag_wait(CTR_DEC, 1);
+    flag_wait(CTR_UDEC, 1);
+    if (xld_word(XW_CLS) == bls::REJ_OK && !xld_word(XW_SINF) && xld_word(XW_UCLS) == bls::REJ_OK &&
+        !xld_word(XW_UINF)) {
+      const MPair m = mpair(dup0(xld(S_UX)), dup0(xld(S_UY)), xld(S_SX), xld(S_SY));
+      const int f1 = team_miller(t1, m, TB1);
+      if (t1.id == 0) xst_word(XW_F1, (uint32_t)f1);
+    }
+  }
+  team_sync(all);
+  sig_cls = team_sig_class();
+  uint8_t ucls = (uint8_t)xld_word(XW_UCLS);
+  if (ucls == bls::REJ_OK && !xld_word(XW_USUB)) ucls = bls::REJ_NOT_IN_SUBGROUP;
+  const uint8_t cls = tlock_class(ucls, sig_cls);
+  e_one = false;
+  if (cls != bls::REJ_OK) return cls;
+  if (xld_word(XW_UINF) || xld_word(XW_SINF)) {  // the pair is skipped: E = 1
+    e_one = true;
+    return cls;
+  }
+  team_final_exp(all, (int)xld_word(XW_F1));
+  return cls;
+}
+
+
 // ------------------------------------------------------------------ VerifyRecovered in two launches
 // The fused threshold round (threshold.cpp spec_recover_launch) verifies the signature it recovers
 // speculatively. Its message and the group key are known from the start, so phase A's hash branch

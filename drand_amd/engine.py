@@ -593,6 +593,27 @@ class Engine:
         self._check(self.lib.blsv_tseal_lat_stats(self._h, ctypes.byref(a), ctypes.byref(b)))
         return a.value, b.value
 
+    def set_tauth_lat_max(self, open_items=None, seal_items=None):
+        """blsv_set_tauth_lat_max: tlock_decrypt_auth / _rounds calls of 1 .. open_items ciphertexts and
+        tlock_encrypt_auth / _rounds calls of 1 .. seal_items messages run on the latency path of the
+        authenticated forms, one workgroup per item (0 = off, the default; None = keep; clamped to the chunk);
+        the outputs are byte for byte the batch path's. A switch of its own: set_tlock_lat_max and
+        set_tseal_lat_max do not move these calls."""
+        keep = ctypes.c_size_t(-1).value
+        return int(self.lib.blsv_set_tauth_lat_max(self._h, keep if open_items is None else int(open_items),
+                                                   keep if seal_items is None else int(seal_items)))
+
+    def tauth_lat_stats(self):
+        """(decrypting latency-path calls, ciphertexts they processed, encrypting latency-path calls, messages
+        they processed) since the context was created."""
+        v = [ctypes.c_uint64() for _ in range(4)]
+        self._check(self.lib.blsv_tauth_lat_stats(self._h, *[ctypes.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def test_tauth_walk_waves(self, waves):
+        """blsv_test_tauth_walk_waves: 8 (the default) or 1 wave for the check's walk on that path."""
+        self._check(self.lib.blsv_test_tauth_walk_waves(self._h, int(waves)))
+
     # ------------------------------------------------------------------ timelock sealing
     # include/blsverify.h "timelock": U_i = k_i G1 and K_i = B^k_i with B = e(pk, H(MessageV2(round)))^3
     # built once per (key, round); tlock_open(sigma_round, U_i) returns K_i.

@@ -781,8 +781,9 @@ int blsv_tlock_encrypt_rounds_dev(blsv_ctx* ctx, const uint8_t* pk48, const uint
  * host forms clear their staged plaintexts too and upload seeds and plaintexts straight from the caller's
  * memory. No constant-time claim, as above.
  *
- * Latency path: the host forms here ALWAYS take the batch path, whatever blsv_set_tlock_lat_max /
- * blsv_set_tseal_lat_max say. There is no service entry and no multi-context form.
+ * Latency path: the host forms here take the batch path whatever blsv_set_tlock_lat_max /
+ * blsv_set_tseal_lat_max say. They have a latency path and a switch of their own, blsv_set_tauth_lat_max
+ * (below), off by default. There is no service entry and no multi-context form.
  *
  * Measured on one MI355X (profiles/tauth_bench.json; 1 Mi items, mlen = 32, the authenticated
  * entry and its mirror alternating call by call, medians): blsv_tlock_decrypt_auth_dev 303.0 ms against 291.2 ms
@@ -819,6 +820,48 @@ int blsv_tlock_decrypt_auth_rounds_dev(blsv_ctx* ctx, const uint8_t* sigs96, con
                                        const uint8_t* d_us48, const uint8_t* d_vs32, const uint8_t* d_ws, size_t mlen,
                                        size_t n, int kdf, uint8_t* d_out_msgs, uint8_t* d_reject_class /*required*/,
                                        uint8_t* d_sig_class /*optional*/, void* stream);
+
+/*
+ * Authenticated timelock on the latency path: for the caller with ONE ciphertext to open or ONE message to
+ * lock, or a handful. With blsv_set_tauth_lat_max(ctx, open_items, seal_items) the HOST forms
+ * blsv_tlock_decrypt_auth and blsv_tlock_decrypt_auth_rounds run calls of 1 .. open_items ciphertexts, and
+ * blsv_tlock_encrypt_auth and blsv_tlock_encrypt_auth_rounds calls of 1 .. seal_items messages, as ONE launch
+ * with one workgroup of eight waves per item (drand_amd/csrc/k_lat_tauth_open.hip, k_lat_tauth_seal.hip,
+ * DESIGN.md 8.9): the whole opening with its re-encryption check, or the whole sealing with the derivation of
+ * its scalar, end to end in the workgroup. Outputs, ok bytes and classes are byte for byte the batch path's,
+ * with the same class precedence; under a sigma that does not decode blsv_tlock_decrypt_auth returns
+ * BLSV_EINVAL with *sig_class set and touches no per-item output. The rounds decrypt takes this path only
+ * while no more than open_items of its signatures are without items. The _dev forms never route.
+ *
+ * A switch of its own: blsv_set_tlock_lat_max and blsv_set_tseal_lat_max do not move these calls, and this one
+ * moves no other. 0 = off (the default, or the environment variables BLSV_TAUTH_OPEN_LAT_MAX /
+ * BLSV_TAUTH_SEAL_LAT_MAX, parsed as BLSV_TSEAL_LAT_MAX is); SIZE_MAX keeps a value as it is. Both values are
+ * clamped to the context's chunk, here and whenever the chunk shrinks. Returns the larger of the two values in
+ * force after the call. blsv_tauth_lat_stats: latency-path calls and the items they processed since the
+ * context's creation, per direction; any pointer may be NULL.
+ *
+ * The path has a device buffer and host staging of its own. The batch paths' counters, blsv_tlock_lat_stats
+ * and blsv_tseal_lat_stats do not move on a routed call; the sigma cache and the (key, round) base cache
+ * survive it; the encrypting side builds the key's table through blsv_tlock_seal_rounds' key cache, whose
+ * *keys counts a table whichever path built it.
+ *
+ * Secrecy on the encrypting side: the derived scalar, k pk and K never leave the workgroup -- K is never
+ * encoded; its SHA-256 midstate is computed from registers and on-chip memory, which the workgroup clears
+ * before it exits -- and the staged seeds and plaintexts, on the device and in the host staging, are cleared
+ * behind the kernel before the entry returns, also when the call fails. There is NO constant-time claim.
+ *
+ * Measured on one MI355X (profiles/tauth_lat_bench.json; host forms, mlen = 32, the two modes
+ * alternating call by call in one run, medians, identical bytes, ok and classes in every pair): a lone
+ * blsv_tlock_decrypt_auth takes 1.81 ms against 19.34 ms on the batch path under a new signature every call
+ * (10.7 times faster) and against 14.64 ms under a cached one (8.1); a lone blsv_tlock_encrypt_auth 1.97 ms
+ * against 34.72 ms to a new round (17.6) and 5.44 ms to a cached one (2.76); 64 items of 64 rounds 1.84 against
+ * 17.69 ms decrypting and 2.00 against 17.83 ms encrypting. The batch path is first faster at n = 2,048
+ * decrypting and at n = 1,024 encrypting. Recommended: blsv_set_tauth_lat_max(ctx, 1024, 512). Authentication
+ * costs 0.27 ms per opening and 0.07 ms per sealing over the unauthenticated forms on their latency paths.
+ */
+size_t blsv_set_tauth_lat_max(blsv_ctx* ctx, size_t open_items, size_t seal_items);
+int blsv_tauth_lat_stats(blsv_ctx* ctx, uint64_t* open_launches, uint64_t* open_items, uint64_t* seal_launches,
+                         uint64_t* seal_items);
 
 /* ---------------------------------------------------------------- thread-safe service
  *

@@ -40,6 +40,14 @@ int blsv_test_final_exp(blsv_ctx* ctx, const uint32_t* f, size_t n, uint32_t* ou
 int blsv_test_tail_split(blsv_ctx* ctx, size_t q);
 
 /*
+ * The waves of a workgroup that share the re-encryption check's table walk on the authenticated timelock's
+ * latency path (blsv_set_tauth_lat_max): 8 (the default: each wave walks eight windows and
+ * three rounds of additions combine the partial sums) or 1 (one wave walks all 64). Both give the same bytes;
+ * tools/tauth_lat_bench.py measures one against the other. BLSV_EINVAL for any other value.
+ */
+int blsv_test_tauth_walk_waves(blsv_ctx* ctx, int waves);
+
+/*
  * Raw operation hook: one named form of the device field / tower arithmetic (drand_amd/csrc/testops.h
  * lists them: fp_*, fp2_*, the one-reduction linear forms, fp4_*, fp6_*, fp12_*, the Miller f pass's
  * LDS forms and the 3-lane tri_* operations) on n items of operands the caller chooses. An item is

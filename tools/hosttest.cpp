@@ -402,6 +402,66 @@ int test_hostlogic() {
              std::to_string(l.o_out) + ", " + std::to_string(l.o_flag) + ", " + std::to_string(l.total) + "]";
     }
   }
+  out += "]}, \"tauth_lat\": {\"routes\": [";
+  {
+    // the authenticated timelock's latency path: the routing predicate as [n, lat_max, routes], the two buffer
+    // layouts at the edge sizes and at the largest n that fits, and the overflow guard just above it
+    const size_t rt[6][2] = {{0, 4}, {1, 4}, {4, 4}, {5, 4}, {1, 0}, {0, 0}};
+    for (int k = 0; k < 6; k++)
+      out += std::string(k ? ", " : "") + "[" + std::to_string(rt[k][0]) + ", " + std::to_string(rt[k][1]) + ", " +
+             (tauth_lat_routes(rt[k][0], rt[k][1]) ? "true" : "false") + "]";
+    const size_t open_most = (SIZE_MAX - 63) / (186 + 2 * 32), seal_most = (SIZE_MAX - 63) / (121 + 2 * 32);
+    const size_t cases[4][2] = {{1, 1}, {3, 33}, {64, 256}, {0, 32}};  // n = 0: the largest n that fits at mlen 32
+    out += "], \"open\": [";
+    bool first = true;
+    for (int k = 0; k < 4; k++)
+      for (int rounds = 0; rounds < 2; rounds++) {
+        const size_t mlen = cases[k][1], idle = rounds && cases[k][0] ? 2 : 0;
+        const size_t n = cases[k][0] ? cases[k][0] : open_most - idle, m = rounds ? n + idle : 1;
+        TauthLatOpenLayout l;
+        CHECK(tauth_lat_open_layout(m, n, rounds != 0, idle, mlen, l));
+        CHECK(l.o_sigof % 4 == 0 && l.o_idle % 4 == 0 && l.o_out % 64 == 0 && l.o_out - l.in_total < 64);
+        CHECK(l.total >= l.o_sigcls && l.total > n && l.out_total == l.total - l.o_out);
+        const size_t v[16] = {m, n, (size_t)rounds, idle, mlen, l.o_us, l.o_vs, l.o_sigof, l.o_idle, l.o_ws, l.in_total,
+                              l.o_out, l.o_cls, l.o_sigcls, l.out_total, l.total};
+        out += std::string(first ? "" : ", ") + "[";
+        first = false;
+        for (int j = 0; j < 16; j++) out += std::string(j ? ", " : "") + std::to_string(v[j]);
+        out += "]";
+      }
+    out += "], \"seal\": [";
+    first = true;
+    for (int k = 0; k < 4; k++)
+      for (int rounds = 0; rounds < 2; rounds++) {
+        const size_t mlen = cases[k][1], n = cases[k][0] ? cases[k][0] : seal_most;
+        TauthLatSealLayout l;
+        CHECK(tauth_lat_seal_layout(n, rounds != 0, mlen, l));
+        CHECK(l.o_seeds % 8 == 0 && l.o_us % 64 == 0 && l.o_us - l.in_total < 64 && l.total > n);
+        const size_t v[12] = {n, (size_t)rounds, mlen, l.o_seeds, l.o_msgs, l.in_total, l.o_us, l.o_vs, l.o_ws, l.o_ok,
+                              l.out_total, l.total};
+        out += std::string(first ? "" : ", ") + "[";
+        first = false;
+        for (int j = 0; j < 12; j++) out += std::string(j ? ", " : "") + std::to_string(v[j]);
+        out += "]";
+      }
+    // just above the largest n, and the lengths outside 1 .. 256: refused, the layout untouched
+    TauthLatOpenLayout ol, okeep;
+    TauthLatSealLayout sl, skeep;
+    CHECK(tauth_lat_open_layout(1, 1, false, 0, 1, ol) && tauth_lat_seal_layout(1, false, 1, sl));
+    okeep = ol;
+    skeep = sl;
+    const bool refused[8] = {!tauth_lat_open_layout(1, open_most + 1, false, 0, 32, ol),
+                             !tauth_lat_open_layout(1, open_most, true, 1, 32, ol),
+                             !tauth_lat_open_layout(1, SIZE_MAX, true, 1, 32, ol),
+                             !tauth_lat_open_layout(3, 1, true, 1, 32, ol),
+                             !tauth_lat_open_layout(1, 1, false, 0, 0, ol) && !tauth_lat_open_layout(1, 1, false, 0, 257, ol),
+                             !tauth_lat_seal_layout(seal_most + 1, true, 32, sl),
+                             !tauth_lat_seal_layout(SIZE_MAX, false, 32, sl),
+                             !tauth_lat_seal_layout(1, false, 0, sl) && !tauth_lat_seal_layout(1, false, 257, sl)};
+    CHECK(ol.total == okeep.total && ol.o_out == okeep.o_out && sl.total == skeep.total && sl.o_us == skeep.o_us);
+    out += "], \"most\": [" + std::to_string(open_most) + ", " + std::to_string(seal_most) + "], \"refused\": [";
+    for (int k = 0; k < 8; k++) out += std::string(k ? ", " : "") + (refused[k] ? "true" : "false");
+  }
   out += "]}, \"open_rounds\": {\"fits\": [";
   {
     // blsv_tlock_open_rounds*: the guard on (counts, m, n) -- the sum must be n without wrapping, and

@@ -15,6 +15,13 @@
 //        wvtest g1comp  < lines "x y" (affine raw hex), or "inf -"     -> the 48 compressed bytes (wseal.h)
 //        wvtest tseal   < lines "pk48 round k32" (round decimal)       -> "ok u48 gt576" (wseal.h seal_item)
 //        wvtest ttseal  < lines "pk48 round k32"                       -> the same by the eight-wave team
+//        wvtest gtmid   < lines "gt576" (hex)                          -> "h2 ks1" from the lane-form midstate (wauth.h)
+//        wvtest awalk   < lines "k" (hex, 0 < k < r)                   -> "u48 -": k G1 by the one-wave walk
+//        wvtest tawalk  < lines "k"                                    -> "u48 n": by the eight waves; n partial sums at infinity
+//        wvtest aopen   < lines "sig96 u48 v32 w" (hex)                -> sigma's class, the item's class, the message bytes
+//        wvtest taopen  < lines "sig96 u48 v32 w"                      -> the same by the eight-wave team
+//        wvtest aseal   < lines "pk48 round seed32 msg mode"           -> "ok u48 v32 w" (mode "-", or "k0": the refusal)
+//        wvtest taseal  < lines "pk48 round seed32 msg mode"           -> the same by the eight-wave team
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
@@ -25,6 +32,7 @@
 #include "../drand_amd/csrc/wrecover.h"
 #include "../drand_amd/csrc/wvteam.h"
 #include "../drand_amd/csrc/wseal.h"
+#include "../drand_amd/csrc/wauth.h"
 #include "../drand_amd/csrc/tseal.h"
 
 #include <thread>
@@ -656,7 +664,227 @@ static int cmd_tseal(bool team) {
   return 0;
 }
 
+// ------------------------------------------------------------------ authenticated timelock (wauth.h)
+static const std::vector<uint32_t>& t1_table() {
+  static const std::vector<uint32_t> T1 =
+      seal_table(bls::g1a{bls::fp_load_const(bls::G1_GEN_X), bls::fp_load_const(bls::G1_GEN_Y)});
+  return T1;
+}
+static void print_words_be(const uint32_t (&w)[8]) {
+  for (int i = 0; i < 8; i++) printf("%08x", w[i]);
+}
+// a hex integer below 2^256 as eight little-endian words
+static void hex_to_k(const std::string& h, uint32_t (&k)[8]) {
+  for (int i = 0; i < 8; i++) k[i] = 0;
+  for (int i = 0; i < (int)h.size() && i < 64; i++) {
+    const char c = h[h.size() - 1 - i];
+    const uint32_t v = c <= '9' ? c - '0' : (c | 32) - 'a' + 10;
+    k[i / 8] |= v << (4 * (i % 8));
+  }
+}
+// run fn(w) as the eight waves of one workgroup
+template <class Fn>
+static void run_team(Fn fn) {
+  for (auto& ctr : g_host_ctr) ctr.store(0);
+  std::thread th[TEAM_WAVES];
+  for (int w = 0; w < TEAM_WAVES; w++)
+    th[w] = std::thread([&, w]() {
+      g_host_wave = w;
+      wv_init();
+      fn(w);
+    });
+  for (auto& t : th) t.join();
+}
+static bool slots_zero(int from, int to) {
+  for (int i = from * 64; i < to * 64; i++)
+    if (g_host_blk[i]) return false;
+  return true;
+}
+
+// gtmid: "gt576" (hex, tlock.h's encoding) -> "h2 ks1": blocks 0 and 1 of tmask.h's key stream from
+// wauth.h gt_midstate over the value in lane form (Montgomery). Aborts unless that midstate is
+// tmask_midstate's over the bytes themselves.
+static int cmd_gtmid() {
+  static char a[1300];
+  while (scanf("%1299s", a) == 1) {
+    wv_init();
+    const std::string h(a);
+    if (h.size() != 1152) {
+      printf("- -\n");
+      continue;
+    }
+    W12 e;
+    for (int c = 0; c < 6; c++) {  // position gt_pos(c): the imaginary part's 96 hex digits, then the real part's
+      const size_t o = 192 * (size_t)gt_pos(c);
+      e.c[c] = to_mont(raw_fp2(h.substr(o + 96, 96), h.substr(o, 96)));
+    }
+    uint32_t mid[8], ref[8], ks[8];
+    gt_midstate(mid, [&](int c) { return e.c[c]; });
+    const auto bytes = unhex(h);
+    uint32_t enc[144];
+    memcpy(enc, bytes.data(), 576);
+    bls::tmask_midstate(ref, [&](int k) { return bls::tmask_coef_enc(enc, k); });
+    if (memcmp(mid, ref, sizeof mid)) fprintf(stderr, "midstate differs from the bytes'\n"), abort();
+    bls::tmask_block(ks, mid, 0);
+    print_words_be(ks);
+    printf(" ");
+    bls::tmask_block(ks, mid, 1);
+    print_words_be(ks);
+    printf("\n");
+    fflush(stdout);
+  }
+  return 0;
+}
+
+// awalk / tawalk: "k" (hex, 0 < k < r) -> the 48 compressed bytes of k G1 by wseal.h seal_walk (one wave)
+// or wauth.h auth_walk_team (one host thread per wave), and the number of partial sums at infinity ("-" for
+// awalk)
+static int cmd_awalk(bool team) {
+  char a[300];
+  while (scanf("%299s", a) == 1) {
+    uint32_t k[8];
+    hex_to_k(a, k);
+    uint32_t u[12];
+    memset(u, 0xee, sizeof u);
+    if (!team) {
+      wv_init();
+      g1_compress_store(u, seal_walk(t1_table().data(), k));
+      print_hex((const uint8_t*)u, 48);
+      printf(" -\n");
+    } else {
+      int n_inf = 0;
+      run_team([&](int w) {
+        Team all = make_team(ALL_WAVES, CTR_ALL);
+        if (w == 0)
+          for (int j = 0; j < TEAM_WAVES; j++) n_inf += g2_is_inf(auth_walk_part(t1_table().data(), k, 8 * j, 8));
+        const G2J s = auth_walk_team(all, t1_table().data(), k);
+        team_sync(all);
+        auth_walk_clear(all);
+        if (w == 3) g1_compress_store(u, s);  // any wave holds the sum
+      });
+      if (!slots_zero(AW_SLOT, AW_SLOT + 3 * TEAM_WAVES)) fprintf(stderr, "partial sums left in their slots\n"), abort();
+      print_hex((const uint8_t*)u, 48);
+      printf(" %d\n", n_inf);
+    }
+    fflush(stdout);
+  }
+  return 0;
+}
+
+// aopen / taopen: "sig96 u48 v32 w" (hex; w: 1 .. 256 bytes) -> "sigma's class, the item's class, the mlen
+// output bytes" through wauth.h auth_open_item (one wave) or auth_open_team (one host thread per wave). The
+// output buffer is guarded on both sides; taopen aborts if the walk's partial sums are left in their slots.
+static int cmd_aopen(bool team) {
+  static char a[300], b[300], c[300], d[600];
+  while (scanf("%299s %299s %299s %599s", a, b, c, d) == 4) {
+    const auto sig = unhex(a), u = unhex(b), v = unhex(c), ws = unhex(d);
+    if (sig.size() != 96 || u.size() != 48 || v.size() != 32 || ws.empty() || ws.size() > 256) {
+      printf("%d %d -\n", bls::REJ_LENGTH, bls::REJ_LENGTH);
+      continue;
+    }
+    const uint32_t mlen = (uint32_t)ws.size();
+    std::vector<uint8_t> out(mlen + 16, 0xee);
+    int cls[TEAM_WAVES], sc[TEAM_WAVES];
+    if (!team) {
+      wv_init();
+      uint8_t s = 0xff;
+      cls[0] = auth_open_item(sig.data(), u.data(), v.data(), ws.data(), mlen, t1_table().data(), out.data() + 8, s);
+      sc[0] = s;
+    } else {
+      run_team([&](int w) {
+        uint8_t s = 0xff;
+        cls[w] = auth_open_team(sig.data(), u.data(), v.data(), ws.data(), mlen, t1_table().data(), out.data() + 8, s);
+        sc[w] = s;
+      });
+      for (int w = 1; w < TEAM_WAVES; w++)
+        if (cls[w] != cls[0] || sc[w] != sc[0]) fprintf(stderr, "waves disagree\n"), abort();
+      if ((cls[0] == 0 || cls[0] == bls::TAUTH_REJ_AUTH) && !slots_zero(AW_SLOT, AW_SLOT + 3 * TEAM_WAVES))
+        fprintf(stderr, "partial sums of k' left in their slots\n"), abort();
+    }
+    for (int i = 0; i < 8; i++)
+      if (out[i] != 0xee || out[8 + mlen + i] != 0xee) fprintf(stderr, "store outside the item's bytes\n"), abort();
+    printf("%d %d ", sc[0], cls[0]);
+    print_hex(out.data() + 8, (int)mlen);
+    printf("\n");
+    fflush(stdout);
+  }
+  return 0;
+}
+
+// aseal / taseal: "pk48 round seed32 msg mode" (round decimal, the rest hex; mode "-" or "k0") -> "ok u48 v32
+// w" through wauth.h auth_seal_item (one wave) or auth_seal_team (one host thread per wave). Mode k0 enters
+// behind the derivation (auth_seal_*_k) with the scalar zero and k_ok false: the refusal's stores, which no
+// known SHA-256 input reaches -- the derivation itself is not part of that line. V and W are guarded on both
+// sides; taseal aborts if a workgroup that sealed leaves anything in the block's LDS slots (K, k pk, ...).
+static int cmd_aseal(bool team) {
+  static char a[300], b[300], c[300], d[600], m[16];
+  std::string tk_key;
+  std::vector<uint32_t> TK;
+  while (scanf("%299s %299s %299s %599s %15s", a, b, c, d, m) == 5) {
+    const auto pk = unhex(a), seed = unhex(c), msg = unhex(d);
+    const uint64_t round = strtoull(b, nullptr, 10);
+    const bool k0 = !strcmp(m, "k0");
+    if (tk_key != a) {
+      bls::g1a P;
+      bool pinf = false;
+      if (pk.size() != 48 || bls::g1_decompress(pk.data(), P, pinf) != bls::REJ_OK || pinf) {
+        printf("-1 - - -\n");
+        continue;
+      }
+      TK = seal_table(P);
+      tk_key = a;
+    }
+    if (seed.size() != 32 || msg.empty() || msg.size() > 256) {
+      printf("-1 - - -\n");
+      continue;
+    }
+    const uint32_t mlen = (uint32_t)msg.size();
+    uint32_t b0[8], u[12];
+    round_b0(round, b0);
+    memset(u, 0xee, sizeof u);
+    std::vector<uint8_t> v(32 + 16, 0xee), w(mlen + 16, 0xee);
+    uint32_t sw[8];
+    const uint32_t kz[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    bls::tauth_seed_words(sw, seed.data());
+    const uint32_t* T1 = t1_table().data();
+    int ok[TEAM_WAVES];
+    if (!team) {
+      wv_init();
+      ok[0] = k0 ? auth_seal_item_k(sw, kz, false, msg.data(), mlen, b0, T1, TK.data(), u, v.data() + 8, w.data() + 8)
+                 : auth_seal_item(seed.data(), msg.data(), mlen, b0, T1, TK.data(), u, v.data() + 8, w.data() + 8);
+    } else {
+      memset(g_host_blk, 0, sizeof g_host_blk);
+      run_team([&](int wv_) {
+        ok[wv_] = k0 ? auth_seal_team_k(sw, kz, false, msg.data(), mlen, b0, T1, TK.data(), u, v.data() + 8, w.data() + 8)
+                     : auth_seal_team(seed.data(), msg.data(), mlen, b0, T1, TK.data(), u, v.data() + 8, w.data() + 8);
+      });
+      for (int i = 1; i < TEAM_WAVES; i++)
+        if (ok[i] != ok[0]) fprintf(stderr, "waves disagree\n"), abort();
+      if (!slots_zero(0, BLK_SLOTS)) fprintf(stderr, "seed-derived values left in the block's slots\n"), abort();
+    }
+    for (int i = 0; i < 8; i++)
+      if (v[i] != 0xee || v[40 + i] != 0xee || w[i] != 0xee || w[8 + mlen + i] != 0xee)
+        fprintf(stderr, "store outside the item's bytes\n"), abort();
+    printf("%d ", ok[0]);
+    print_hex((const uint8_t*)u, 48);
+    printf(" ");
+    print_hex(v.data() + 8, 32);
+    printf(" ");
+    print_hex(w.data() + 8, (int)mlen);
+    printf("\n");
+    fflush(stdout);
+  }
+  return 0;
+}
+
 int main(int argc, char** argv) {
+  if (argc >= 2 && !strcmp(argv[1], "gtmid")) return cmd_gtmid();
+  if (argc >= 2 && !strcmp(argv[1], "awalk")) return cmd_awalk(false);
+  if (argc >= 2 && !strcmp(argv[1], "tawalk")) return cmd_awalk(true);
+  if (argc >= 2 && !strcmp(argv[1], "aopen")) return cmd_aopen(false);
+  if (argc >= 2 && !strcmp(argv[1], "taopen")) return cmd_aopen(true);
+  if (argc >= 2 && !strcmp(argv[1], "aseal")) return cmd_aseal(false);
+  if (argc >= 2 && !strcmp(argv[1], "taseal")) return cmd_aseal(true);
   if (argc >= 2 && !strcmp(argv[1], "tscalar")) return cmd_tscalar();
   if (argc >= 2 && !strcmp(argv[1], "g1comp")) return cmd_g1comp();
   if (argc >= 2 && !strcmp(argv[1], "tseal")) return cmd_tseal(false);
