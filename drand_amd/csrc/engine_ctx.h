@@ -48,7 +48,8 @@ static_assert(kHqWords(kMaxChunk) <= (blsk::HQ_WORDS + 3) * kMaxChunk, "kStaging
 //              (it used to double as the park: a split pass's remainder still reads its lines while
 //              the main range is in its final exponentiation)
 //   F          the f pass writes; the final exponentiation consumes and reuses as scratch
-//   FW         the 3-lane f pass parks in it; then the final exponentiation's G, B, C
+//   FW         the 3-lane f pass parks in it; then the final exponentiation's three slots (k_fexp.hip:
+//              g then b, g^3, c)
 // A split pass (hostlogic.h tail_split_main, verify.cpp pairing_check): after the f pass of the main
 // range [0, main) the side stream runs the f pass and the final exponentiation of [main, cnt) beside the
 // main range's final exponentiation on the launch stream. The two touch disjoint columns of F, FW and

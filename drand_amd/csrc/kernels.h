@@ -72,6 +72,8 @@ constexpr size_t TRI_PARK_WORDS(size_t items) { return 48 * 64 * ((items + 20) /
 // The final exponentiation of the m items [base, base + m) of a pass whose staging has stride n: their
 // columns of F are clobbered; W = 3 * n * F_WORDS words of staging (the range's columns are used); out
 // (optional: test hook, timelock): the exponentiated values (SoA of stride n, the range's columns).
+// cls gets REJ_PAIRING where the value is not 1; without out that is decided by a comparison and the
+// value itself is never formed (pairing.h fexp_step4_is_one).
 // park: FEXP_PARK_WORDS(m) words of scratch for the 3-lane products' parked partial results; ranges
 // that run side by side need disjoint park areas.
 constexpr size_t FEXP_PARK_WORDS(size_t items) { return TRI_PARK_WORDS(items); }

@@ -332,20 +332,31 @@ DI fp12 miller_loop_multi(const g1a (&P)[NP], const g2a (&Q)[NP], const bool (&a
 // each use through the `load` callables instead of being held in registers):
 //   easy : g = f^((p^6 - 1)(p^2 + 1))
 //   hard : 3 (p^4 - p^2 + 1)/r = (x-1)^2 (x+p) (x^2+p^2-1) + 3 with x = -|x|, i.e.
-//     a = g^(x-1)           step<0>(g)
+//     a = g^(x-1)           step<0>(g), which also hands out g^3
 //     b = a^(x-1)           step<1>(a)
 //     c = b^(x+p)           step<2>(b)
 //     t = c^x               step<3>(c)
-//     e = t^x c^(p^2) c^-1 g^3   step<4>(t; c, g)
+//     e = t^x g^3 c^(p^4)   step<4>(t; c, g^3)
 // g^|x| uses Granger-Scott cyclotomic squarings; |x| = 0xd201000000010000 has bits 63,62,60,57,48,16,
 // i.e. runs of 1, 2, 3, 9, 32 squarings each followed by a multiplication, then 16 squarings.
+// Three identities keep step<4> short:
+//   - c lies in the cyclotomic subgroup (c^(p^4 - p^2 + 1) = 1), so c^(p^2) c^-1 = c^(p^4), and the
+//     p^4 Frobenius is a product by a constant of Fp per coefficient (tower.h fp12_frob4);
+//   - |x| starts with the bits 11, so the running value of step<0>'s x-power after its first square
+//     and first product is g^3: fp12_pow_x_abs_reload hands it to `cube` there;
+//   - the inverse of a cyclotomic element is its conjugate, so e == 1 exactly when
+//     t^x g^3 == conj(c^(p^4)): the verdict (fexp_step4_is_one) needs no product with c.
 DI fp12 fexp_easy(const fp12& f) {
   fp12 t = fp12_mul(fp12_conj(f), fp12_inv(f));  // f^(p^6 - 1)
   return fp12_mul(fp12_frob2(t), t);             // ^(p^2 + 1)
 }
 
-template <typename Load>
-DI fp12 fp12_pow_x_abs_reload(Load load) {
+struct fexp_no_cube {
+  DI void operator()(const fp12&) const {}
+};
+
+template <typename Load, typename Cube>
+DI fp12 fp12_pow_x_abs_reload(Load load, Cube cube) {
   constexpr uint64_t NSQ = 1ull | (2ull << 6) | (3ull << 12) | (9ull << 18) | (32ull << 24) | (16ull << 30);
   fp12 r = load();
 #pragma unroll 1
@@ -354,31 +365,54 @@ DI fp12 fp12_pow_x_abs_reload(Load load) {
 #pragma unroll 1
     for (int k = 0; k < n; k++) r = fp12_cyclotomic_sqr(r);
     if (s < 5) r = fp12_mul(r, load());
+    if (s == 0) cube(r);  // X^2 X
   }
   return r;
 }
 
-template <int MODE, typename LX, typename LC, typename LG>
-DI fp12 fexp_step(LX lx, LC lc, LG lg) {
-  fp12 r = fp12_conj(fp12_pow_x_abs_reload(lx));  // X^x (inverse = conjugate in the cyclotomic subgroup)
+// lg3 loads g^3 (MODE 4); cube receives X^3 (MODE 0: X = g)
+template <int MODE, typename LX, typename LC, typename LG3, typename Cube>
+DI fp12 fexp_step(LX lx, LC lc, LG3 lg3, Cube cube) {
+  fp12 r = fp12_conj(fp12_pow_x_abs_reload(lx, cube));  // X^x (inverse = conjugate in the cyclotomic subgroup)
   if (MODE == 0 || MODE == 1) return fp12_mul(r, fp12_conj(lx()));
   if (MODE == 2) return fp12_mul(r, fp12_frob(lx()));
   if (MODE == 3) return r;
-  r = fp12_mul(r, fp12_frob2(lc()));
-  r = fp12_mul(r, fp12_conj(lc()));
-  r = fp12_mul(r, fp12_cyclotomic_sqr(lg()));
-  return fp12_mul(r, lg());
+  r = fp12_mul(r, lg3());
+  return fp12_mul(r, fp12_frob4(lc()));
 }
 
-// whole final exponentiation in registers (host op counter, test hooks)
+// step<4>'s verdict e == 1 without e. For g = 0 (a zero f: no pairing value) every staged value is
+// zero and e = 0 is not one: the zero test keeps that.
+template <typename LX, typename LC, typename LG3>
+DI bool fexp_step4_is_one(LX lx, LC lc, LG3 lg3) {
+  const fp12 r = fp12_mul(fp12_conj(fp12_pow_x_abs_reload(lx, fexp_no_cube())), lg3());
+  return fp12_eq(r, fp12_conj(fp12_frob4(lc()))) & !fp12_is_zero(r);
+}
+
+// the staged values of the hard part up to step<3>, in registers
+struct fexp_staged {
+  fp12 g, g3, c, t;
+};
+DI fexp_staged fexp_stage_to_t(const fp12& f) {
+  fexp_staged s;
+  s.g = fexp_easy(f);
+  auto none = [&]() { return s.g; };
+  const fexp_no_cube nc;
+  const fp12 a = fexp_step<0>([&]() { return s.g; }, none, none, [&](const fp12& v) { s.g3 = v; });
+  const fp12 b = fexp_step<1>([&]() { return a; }, none, none, nc);
+  s.c = fexp_step<2>([&]() { return b; }, none, none, nc);
+  s.t = fexp_step<3>([&]() { return s.c; }, none, none, nc);
+  return s;
+}
+
+// whole final exponentiation in registers (host op counter, test hooks): the value, and the verdict
 DI fp12 final_exponentiation(const fp12& f) {
-  const fp12 g = fexp_easy(f);
-  auto none = [&]() { return g; };
-  const fp12 a = fexp_step<0>([&]() { return g; }, none, none);
-  const fp12 b = fexp_step<1>([&]() { return a; }, none, none);
-  const fp12 c = fexp_step<2>([&]() { return b; }, none, none);
-  const fp12 t = fexp_step<3>([&]() { return c; }, none, none);
-  return fexp_step<4>([&]() { return t; }, [&]() { return c; }, [&]() { return g; });
+  const fexp_staged s = fexp_stage_to_t(f);
+  return fexp_step<4>([&]() { return s.t; }, [&]() { return s.c; }, [&]() { return s.g3; }, fexp_no_cube());
+}
+DI bool final_exponentiation_is_one(const fp12& f) {
+  const fexp_staged s = fexp_stage_to_t(f);
+  return fexp_step4_is_one([&]() { return s.t; }, [&]() { return s.c; }, [&]() { return s.g3; });
 }
 
 }  // namespace bls

@@ -578,6 +578,7 @@ DI fp6 fp6_inv(const fp6& a) {
 DI fp12 fp12_one() { return {fp6_one(), fp6_zero()}; }
 DI bool fp12_eq(const fp12& a, const fp12& b) { return fp6_eq(a.c0, b.c0) & fp6_eq(a.c1, b.c1); }
 DI bool fp12_is_one(const fp12& a) { return fp12_eq(a, fp12_one()); }
+DI bool fp12_is_zero(const fp12& a) { return fp12_eq(a, {fp6_zero(), fp6_zero()}); }
 DI fp12 fp12_conj(const fp12& a) { return {a.c0, fp6_neg(a.c1)}; }  // a^(p^6)
 
 DI fp12 fp12_mul(const fp12& a, const fp12& b) {  // Karatsuba, 3 Fp6 mul
@@ -669,6 +670,20 @@ DI fp12 fp12_frob2(const fp12& a) {  // gamma2^k lies in Fp
   r.c1.c1 = fp2_mul_fp(a.c1.c1, fp_load_const(FROB2_GAMMA[3][0]));
   r.c0.c2 = fp2_mul_fp(a.c0.c2, fp_load_const(FROB2_GAMMA[4][0]));
   r.c1.c2 = fp2_mul_fp(a.c1.c2, fp_load_const(FROB2_GAMMA[5][0]));
+  return r;
+}
+
+// a^(p^4) = sum c_k gamma2^(2k) w^k: gamma2 is a sixth root of unity in Fp, so gamma2^(2k) is
+// FROB2_GAMMA[2k mod 6] and c_0, c_3 stay as they are
+DI fp12 fp12_frob4(const fp12& a) {
+  const fp g2 = fp_load_const(FROB2_GAMMA[2][0]), g4 = fp_load_const(FROB2_GAMMA[4][0]);
+  fp12 r;
+  r.c0.c0 = a.c0.c0;
+  r.c1.c0 = fp2_mul_fp(a.c1.c0, g2);
+  r.c0.c1 = fp2_mul_fp(a.c0.c1, g4);
+  r.c1.c1 = a.c1.c1;
+  r.c0.c2 = fp2_mul_fp(a.c0.c2, g2);
+  r.c1.c2 = fp2_mul_fp(a.c1.c2, g4);
   return r;
 }
 

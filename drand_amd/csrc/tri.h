@@ -589,6 +589,28 @@ DI fp4 tri_frob2(const tri_lane& t, const fp4& x) {
   return {fp2_mul_fp(x.a, ga), fp2_mul_fp(x.b, gb)};
 }
 
+// f^(p^4): c_k -> c_k gamma2^(2k) (tower.h fp12_frob4). Lane j holds c_j and c_(j+3), whose constants
+// are equal (gamma2^6 = 1): role 0 keeps its third, role 1 takes gamma2^2, role 2 gamma2^4.
+DI fp4 tri_frob4(const tri_lane& t, const fp4& x) {
+  const fp g = fp_select(t.role == 1, fp_load_const(FROB2_GAMMA[2][0]), fp_load_const(FROB2_GAMMA[4][0]));
+  const fp4 y = {fp2_mul_fp(x.a, g), fp2_mul_fp(x.b, g)};
+  return fp4_select(t.role == 0, x, y);
+}
+
+// x == y as Fp12 (thirds in [0, 2p), compared mod p), combined over the group
+DI bool tri_eq(const tri_lane& t, const fp4& x, const fp4& y) {
+  const int mine = (fp2_eq(x.a, y.a) & fp2_eq(x.b, y.b)) ? 1 : 0;
+  const int n1 = __builtin_amdgcn_ds_bpermute(t.next_b, mine);
+  const int n2 = __builtin_amdgcn_ds_bpermute(t.prev_b, mine);
+  return (mine & n1 & n2) != 0;
+}
+DI bool tri_is_zero(const tri_lane& t, const fp4& x) {
+  const int mine = (fp2_is_zero(x.a) & fp2_is_zero(x.b)) ? 1 : 0;
+  const int n1 = __builtin_amdgcn_ds_bpermute(t.next_b, mine);
+  const int n2 = __builtin_amdgcn_ds_bpermute(t.prev_b, mine);
+  return (mine & n1 & n2) != 0;
+}
+
 // this lane's part of "f == 1": role 0 must hold (1, 0), roles 1, 2 zero; combined over the group
 DI bool tri_is_one(const tri_lane& t, const fp4& x) {
   const fp2 want_a = fp2_select(t.role == 0, fp2_one(), fp2_zero());
