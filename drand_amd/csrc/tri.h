@@ -135,45 +135,6 @@ DI fp4 fp4_sqr_k7(const fp4& x) {
   return y;
 }
 
-}  // namespace bls
-
-#ifndef BLS_HOST
-namespace bls {
-
-constexpr int TRI_GROUPS = 21;  // beacons per 64-lane wave
-
-// per-lane LDS columns of the staged product operands (see "low register pressure products" below)
-constexpr int TRI_ARG_WORDS = 72;
-static __shared__ __attribute__((aligned(16))) uint32_t g_tri_arg[TRI_ARG_WORDS * BLS_LANES];
-
-// role-dependent additions as one fp_addsub (direction as data) instead of both results + a select
-
-DI fp4 fp4_add(const fp4& x, const fp4& y) { return {fp2_add(x.a, y.a), fp2_add(x.b, y.b)}; }
-DI fp4 fp4_sub(const fp4& x, const fp4& y) { return {fp2_sub(x.a, y.a), fp2_sub(x.b, y.b)}; }
-DI fp4 fp4_dbl(const fp4& x) { return {fp2_dbl(x.a), fp2_dbl(x.b)}; }
-DI fp4 fp4_add_lazy(const fp4& x, const fp4& y) { return {fp2_add_lazy(x.a, y.a), fp2_add_lazy(x.b, y.b)}; }
-DI fp4 fp4_addsub(const fp4& x, const fp4& y, bool sub) { return {fp2_addsub(x.a, y.a, sub), fp2_addsub(x.b, y.b, sub)}; }
-DI fp4 fp4_select(bool c, const fp4& x, const fp4& y) { return {fp2_select(c, x.a, y.a), fp2_select(c, x.b, y.b)}; }
-// x * s = xi b + a s
-DI fp4 fp4_mul_s(const fp4& x) { return {fp2_mul_xi(x.b), x.a}; }
-
-// (xa + xb s)(ya + yb s) = xa ya + xi xb yb + ((xa + xb)(ya + yb) - xa ya - xb yb) s: 3 Fp2 products
-DI fp4 fp4_mul(const fp4& x, const fp4& y) {
-  const fp2 t0 = fp2_mul(x.a, y.a);
-  const fp2 t1 = fp2_mul(x.b, y.b);
-  const fp2 t2 = fp2_mul(fp2_add_lazy(x.a, x.b), fp2_add_lazy(y.a, y.b));
-  return {fp2_add(t0, fp2_mul_xi(t1)), fp2_sub(fp2_sub(t2, t0), t1)};
-}
-
-// (a + b s)^2 = a^2 + xi b^2 + ((a + b)^2 - a^2 - b^2) s: 3 Fp2 squares, expanded in place (the
-// cyclotomic squaring loop is call-free so its kernel keeps a small register budget)
-DI fp4 fp4_sqr_inl(const fp4& x) {
-  const fp2 t0 = fp2_sqr_inl(x.a);
-  const fp2 t1 = fp2_sqr_inl(x.b);
-  const fp2 t2 = fp2_sqr_inl(fp2_add_lazy(x.a, x.b));
-  return {fp2_add(t0, fp2_mul_xi(t1)), fp2_sub(fp2_sub(t2, t0), t1)};
-}
-
 // (a + b s)^2 = (a^2 + xi b^2) + 2ab s as four Montgomery dot products, for a, b < 2p (one reduction
 // per output component instead of two per Fp2 square, and no additions after the products):
 //   Y.a.c0 = (a0 + a1)(a0 - a1) + (b0 + b1)(b0 - b1) + (2 b0)(-b1)      Y.a.c1 = (2 a0) a1 + (b0 + b1)(b0 - b1) + (2 b0) b1
@@ -211,6 +172,194 @@ DI fp4 fp4_sqr_dot(const fp4& x) {
   BLS_SCHED_FENCE();
   y.b.c1 = fp_from_u12(fp_mont_dot3<2>(a02, b1, a12, b0, a12, b0));
   return y;
+}
+
+// The same square with SIX product columns and four reductions in ONE body: Y.b = 2ab comes out of
+// the square of the limb-wise sum s = a + b (s0 = a0 + b0, s1 = a1 + b1, limbs < 2^29, no carry)
+//   S0 = (s0 + s1)(s0 - s1)   S1 = (2 s0) s1
+//   Y.b.c0 = S0 - A - T = 2(a0 b0 - a1 b1)      Y.b.c1 = S1 - C - V = 2(a0 b1 + a1 b0)
+// next to Y.a.c0 = A + T - V and Y.a.c1 = C + T + V of fp4_sqr_ya_t: A + T and C + V are each one
+// product stream (X, W), T and V one each, S0 and S1 run straight into their accumulators.
+// Operands: s0 + s1 < 2^30 and |s0 - s1| < 2^29 fit v_mad_i64_i32, 2 s0 < 2^30 and s1 < 2^29 fit
+// v_mad_u64_u32. One S0 or S1 column reaches 14 * 2^59, and with A and T next to it a partial sum of
+// c2 / c3 can pass 2^63. That is harmless: convolution is bilinear, so S0_k - A_k - T_k =
+// 2 (a0 b0 - a1 b1)_k and S1_k - C_k - V_k = 2 (a0 b1 + a1 b0)_k hold column by column, and once a
+// column is complete, which is the only moment its accumulator is shifted, the true value is
+// |column| < 2 * 2 * 14 * 2^56 < 2^61.8, plus the reduction < 14 * 2^56, plus the carry (< 2^35):
+// inside a signed 64-bit word. The accumulators are uint64_t (wrap-around modulo 2^64 is exact and
+// defined), read as signed only for the arithmetic >> 28 and the final sign.
+// Ranges for a, b < 2p, with 0 <= m p < R p and p / R < 1 / 2520:
+//   Y.b.c0 = (2 (a0 b0 - a1 b1) + m p) / R,  |2 (a0 b0 - a1 b1)| < 8 p^2:  in (-p/315, p + p/315),
+//            inside (-p/256, 2p): one conditional + p like Y.a
+//   Y.b.c1 = (2 (a0 b1 + a1 b0) + m p) / R,  0 <= 2 (..) < 16 p^2:         in [0, p + p/157)
+//   Y.a as fp4_sqr_ya_t.
+//
+// The four accumulators pass through one empty volatile asm at the end of every column. Without it
+// the compiler finishes Y.b's two chains first and runs Y.a's reductions after them, with the column
+// sums of X, W, T and V parked in between: 83 scratch instructions per square. sched_barrier does
+// not help: the order is chosen before the machine scheduler runs. With it every column's four sums
+// are complete before the next column starts, and the body holds no scratch access.
+// This leans on how the compiler orders the block, so after a toolchain change re-check k_fexp_tri<0..4>
+// (build/k_fexp.o): tools/kinfo.py must show 256 registers and at most 96 / 128 / 192 / 64 / 160 B/lane of
+// scratch, and the disassembly no scratch_ instruction inside the squaring loop (1,961 MADs per pass).
+#ifdef BLS_HOST
+#define BLS_K6_COLUMN_SYNC(c0, c1, c2, c3) ((void)0)
+#else
+#define BLS_K6_COLUMN_SYNC(c0, c1, c2, c3) asm volatile("" : "+v"(c0), "+v"(c1), "+v"(c2), "+v"(c3))
+#endif
+DI void fp4_sqr_k6_t(const uint32_t (&a0)[14], const uint32_t (&a1)[14], const uint32_t (&b0)[14],
+                     const uint32_t (&b1)[14], uint32_t (&t0)[14], uint32_t (&t1)[14], uint32_t (&t2)[14],
+                     uint32_t (&t3)[14], bool& neg0, bool& neg1, bool& neg2) {
+  int32_t am[14], bm[14], sm[14];
+  uint32_t ap[14], bp[14], sp[14], a02[14], b02[14], s02[14], s1[14];
+#pragma unroll
+  for (int k = 0; k < 14; k++) {
+    ap[k] = a0[k] + a1[k];
+    am[k] = (int32_t)a0[k] - (int32_t)a1[k];
+    bp[k] = b0[k] + b1[k];
+    bm[k] = (int32_t)b0[k] - (int32_t)b1[k];
+    a02[k] = a0[k] << 1;
+    b02[k] = b0[k] << 1;
+    sp[k] = ap[k] + bp[k];
+    sm[k] = am[k] + bm[k];
+    s02[k] = a02[k] + b02[k];
+    s1[k] = a1[k] + b1[k];
+  }
+  uint32_t m0[14], m1[14], m2[14], m3[14];
+  uint64_t c0 = 0, c1 = 0, c2 = 0, c3 = 0;
+#pragma unroll
+  for (int k = 0; k < 27; k++) {
+    const int lo = k > 13 ? k - 13 : 0, hi = k < 13 ? k : 13;
+    // the c0 family (ap, am, bp, bm, sp, sm), then the c1 family (a02, a1, b02, b1, s02, s1)
+    uint64_t T = 0, V = 0;
+#pragma unroll
+    for (int j = lo; j <= hi; j++) T += (uint64_t)((int64_t)(int32_t)bp[j] * (int64_t)bm[k - j]);
+    uint64_t X = T;  // X = A + T
+#pragma unroll
+    for (int j = lo; j <= hi; j++) X += (uint64_t)((int64_t)(int32_t)ap[j] * (int64_t)am[k - j]);
+#pragma unroll
+    for (int j = lo; j <= hi; j++) c2 += (uint64_t)((int64_t)(int32_t)sp[j] * (int64_t)sm[k - j]);
+#pragma unroll
+    for (int j = lo; j <= hi; j++) V += (uint64_t)b02[j] * b1[k - j];
+    uint64_t W = V;  // W = C + V
+#pragma unroll
+    for (int j = lo; j <= hi; j++) W += (uint64_t)a02[j] * a1[k - j];
+#pragma unroll
+    for (int j = lo; j <= hi; j++) c3 += (uint64_t)s02[j] * s1[k - j];
+    c0 += X - V;
+    c1 += W + T;
+    c2 -= X;
+    c3 -= W;
+    if (k < 14) {
+#pragma unroll
+      for (int j = 0; j < k; j++) {
+        c0 += (uint64_t)m0[j] * P28[k - j];
+        c1 += (uint64_t)m1[j] * P28[k - j];
+        c2 += (uint64_t)m2[j] * P28[k - j];
+        c3 += (uint64_t)m3[j] * P28[k - j];
+      }
+      m0[k] = ((uint32_t)c0 * P_INV28) & M28;
+      m1[k] = ((uint32_t)c1 * P_INV28) & M28;
+      m2[k] = ((uint32_t)c2 * P_INV28) & M28;
+      m3[k] = ((uint32_t)c3 * P_INV28) & M28;
+      c0 += (uint64_t)m0[k] * P28[0];
+      c1 += (uint64_t)m1[k] * P28[0];
+      c2 += (uint64_t)m2[k] * P28[0];
+      c3 += (uint64_t)m3[k] * P28[0];
+    } else {
+#pragma unroll
+      for (int j = k - 13; j < 14; j++) {
+        c0 += (uint64_t)m0[j] * P28[k - j];
+        c1 += (uint64_t)m1[j] * P28[k - j];
+        c2 += (uint64_t)m2[j] * P28[k - j];
+        c3 += (uint64_t)m3[j] * P28[k - j];
+      }
+      t0[k - 14] = (uint32_t)c0 & M28;
+      t1[k - 14] = (uint32_t)c1 & M28;
+      t2[k - 14] = (uint32_t)c2 & M28;
+      t3[k - 14] = (uint32_t)c3 & M28;
+    }
+    c0 = (uint64_t)((int64_t)c0 >> 28);  // arithmetic: the completed column sums are signed
+    c1 = (uint64_t)((int64_t)c1 >> 28);
+    c2 = (uint64_t)((int64_t)c2 >> 28);
+    c3 = (uint64_t)((int64_t)c3 >> 28);
+    BLS_K6_COLUMN_SYNC(c0, c1, c2, c3);
+  }
+  t0[13] = (uint32_t)c0;
+  t1[13] = (uint32_t)c1;
+  t2[13] = (uint32_t)c2;
+  t3[13] = (uint32_t)c3;
+  neg0 = (int64_t)c0 < 0;
+  neg1 = (int64_t)c1 < 0;
+  neg2 = (int64_t)c2 < 0;
+}
+
+DI fp4 fp4_sqr_k6(const fp4& x) {
+  uint32_t a0[14], a1[14], b0[14], b1[14];
+  fp_split28(fp_to_u12(x.a.c0), a0);
+  fp_split28(fp_to_u12(x.a.c1), a1);
+  fp_split28(fp_to_u12(x.b.c0), b0);
+  fp_split28(fp_to_u12(x.b.c1), b1);
+  uint32_t t0[14], t1[14], t2[14], t3[14];
+  bool n0, n1, n2;
+  fp4_sqr_k6_t(a0, a1, b0, b1, t0, t1, t2, t3, n0, n1, n2);
+  fp4 y;
+  y.a.c0 = fp_from_u12(fp_join28_fix(t0, n0));
+  y.a.c1 = fp_from_u12(fp_join28_fix(t1, n1));
+  y.b.c0 = fp_from_u12(fp_join28_fix(t2, n2));
+  y.b.c1 = fp_from_u12(fp_join28(t3));
+  return y;
+}
+
+// the Fp4 square of the cyclotomic squaring (tri_cyclotomic_sqr below; the host build's three-lane
+// emulation in tools/opcount): the one-body six-column form, else the seven-column one, else the dot products
+#ifndef BLS_FP4_SQR_K6
+#define BLS_FP4_SQR_K6 1
+#endif
+#ifndef BLS_FP4_SQR_K7
+#define BLS_FP4_SQR_K7 1
+#endif
+DI fp4 fp4_sqr_cyc(const fp4& x) {
+  return BLS_FP4_SQR_K6 ? fp4_sqr_k6(x) : (BLS_FP4_SQR_K7 ? fp4_sqr_k7(x) : fp4_sqr_dot(x));
+}
+
+}  // namespace bls
+
+#ifndef BLS_HOST
+namespace bls {
+
+constexpr int TRI_GROUPS = 21;  // beacons per 64-lane wave
+
+// per-lane LDS columns of the staged product operands (see "low register pressure products" below)
+constexpr int TRI_ARG_WORDS = 72;
+static __shared__ __attribute__((aligned(16))) uint32_t g_tri_arg[TRI_ARG_WORDS * BLS_LANES];
+
+// role-dependent additions as one fp_addsub (direction as data) instead of both results + a select
+
+DI fp4 fp4_add(const fp4& x, const fp4& y) { return {fp2_add(x.a, y.a), fp2_add(x.b, y.b)}; }
+DI fp4 fp4_sub(const fp4& x, const fp4& y) { return {fp2_sub(x.a, y.a), fp2_sub(x.b, y.b)}; }
+DI fp4 fp4_dbl(const fp4& x) { return {fp2_dbl(x.a), fp2_dbl(x.b)}; }
+DI fp4 fp4_add_lazy(const fp4& x, const fp4& y) { return {fp2_add_lazy(x.a, y.a), fp2_add_lazy(x.b, y.b)}; }
+DI fp4 fp4_addsub(const fp4& x, const fp4& y, bool sub) { return {fp2_addsub(x.a, y.a, sub), fp2_addsub(x.b, y.b, sub)}; }
+DI fp4 fp4_select(bool c, const fp4& x, const fp4& y) { return {fp2_select(c, x.a, y.a), fp2_select(c, x.b, y.b)}; }
+// x * s = xi b + a s
+DI fp4 fp4_mul_s(const fp4& x) { return {fp2_mul_xi(x.b), x.a}; }
+
+// (xa + xb s)(ya + yb s) = xa ya + xi xb yb + ((xa + xb)(ya + yb) - xa ya - xb yb) s: 3 Fp2 products
+DI fp4 fp4_mul(const fp4& x, const fp4& y) {
+  const fp2 t0 = fp2_mul(x.a, y.a);
+  const fp2 t1 = fp2_mul(x.b, y.b);
+  const fp2 t2 = fp2_mul(fp2_add_lazy(x.a, x.b), fp2_add_lazy(y.a, y.b));
+  return {fp2_add(t0, fp2_mul_xi(t1)), fp2_sub(fp2_sub(t2, t0), t1)};
+}
+
+// (a + b s)^2 = a^2 + xi b^2 + ((a + b)^2 - a^2 - b^2) s: 3 Fp2 squares, expanded in place (the
+// cyclotomic squaring loop is call-free so its kernel keeps a small register budget)
+DI fp4 fp4_sqr_inl(const fp4& x) {
+  const fp2 t0 = fp2_sqr_inl(x.a);
+  const fp2 t1 = fp2_sqr_inl(x.b);
+  const fp2 t2 = fp2_sqr_inl(fp2_add_lazy(x.a, x.b));
+  return {fp2_add(t0, fp2_mul_xi(t1)), fp2_sub(fp2_sub(t2, t0), t1)};
 }
 
 DI fp4 fp4_sqr(const fp4& x) {
@@ -274,9 +423,6 @@ DI fp4 tri_conj(const tri_lane& t, const fp4& x) {
 // each lane squares its Fp4 (X = A_j^2); roles 1 and 2 swap their squares; then
 //   role 0, 2: (a, b) <- (3 Y.a - 2 a, 3 Y.b + 2 b)     (role 0: Y = own square, role 2: role 1's)
 //   role 1:    (a, b) <- (3 xi Y.b + 2 a, 3 Y.a - 2 b)  (Y = role 2's square)
-#ifndef BLS_FP4_SQR_K7
-#define BLS_FP4_SQR_K7 1
-#endif
 #ifndef BLS_CSQR_PARK
 #define BLS_CSQR_PARK 1
 #endif
@@ -322,7 +468,7 @@ DI fp4 tri_cyclotomic_sqr(const tri_lane& t, const fp4& x_in) {
   tri_park4(x_in);
   asm volatile("" ::: "memory");  // the park is neither sunk below the square nor forwarded past it
 #endif
-  const fp4 sq = BLS_FP4_SQR_K7 ? fp4_sqr_k7(x_in) : fp4_sqr_dot(x_in);
+  const fp4 sq = fp4_sqr_cyc(x_in);
   const int src = t.role == 1 ? t.next_b : (t.role == 2 ? t.prev_b : (int)(4u * t.lane));
   const fp4 y = xchg_fp4(sq, src);
 #if BLS_CSQR_PARK

@@ -433,6 +433,137 @@ static int cmd_f6fuzz(unsigned long n) {
   return bad ? 1 : 0;
 }
 
+// tri.h fp4_sqr_k6 (six product columns, four reductions, one body; wrap-around accumulators) against
+// fp4_sqr_dot, fp4_sqr_k7 and three fp2_sqr / fp2_mul; every output must lie in [0, 2p). Inputs: random
+// operands in [0, 2p); 0, p - 1, p and 2p - 1 in every component (all 256 combinations); operands whose
+// limbs below the top one are all 2^28 - 1 (the largest columns: the partial sums of Y.b pass 2^63);
+// the operands that make Y.b.c0 and Y.a.c0 as negative and as large as they get; operands built so that
+// Y.b.c0 is exactly -2^k before its + p, each of which must take that branch. Then the whole
+// Granger-Scott square of the three-lane layout (three Fp4 squares by the form this build selects,
+// tri.h fp4_sqr_cyc, and the role combinations of tri_cyclotomic_sqr) against tower.h
+// fp12_cyclotomic_sqr on cyclotomic values, 63 squares in a row per value.
+static int cmd_sq6fuzz(unsigned long n) {
+  using namespace bls;
+  unsigned long long s = 0x6a09e667f3bcc909ull;
+  auto next = [&]() {
+    s ^= s << 13, s ^= s >> 7, s ^= s << 17;
+    return (uint32_t)(s >> 11);
+  };
+  auto rnd = [&]() {  // uniform top word below 2p's: the value is < 2p
+    fp x;
+    for (int i = 0; i < 11; i++) x.l[i] = next();
+    x.l[11] = next() % P2_RAW[11];
+    return x;
+  };
+  auto lt2p = [](const fp& a) {
+    unsigned br = 0;
+    for (int i = 0; i < 12; i++) (void)__builtin_subc(a.l[i], P2_RAW[i], br, &br);
+    return br != 0;
+  };
+  fp edge[4];  // 0, p - 1, p, 2p - 1
+  edge[0] = fp_zero();
+  for (int i = 0; i < 12; i++) edge[1].l[i] = P_RAW[i] - (i == 0), edge[2].l[i] = P_RAW[i], edge[3].l[i] = P2_RAW[i] - (i == 0);
+  // every limb below the top one 2^28 - 1 (bits 0 .. 363 set), the top limb `top` (< 2p's top limb)
+  auto full = [&](uint32_t top) {
+    fp x;
+    for (int i = 0; i < 11; i++) x.l[i] = 0xffffffffu;
+    x.l[11] = (top << 12) | 0xfffu;
+    return x;
+  };
+  const uint32_t top2p = P2_RAW[11] >> 12;  // 2p's top limb; full(top2p - 1) < 2p
+  unsigned long bad = 0, cases = 0, negfix = 0;
+  auto check = [&](const fp4& x) -> bool {
+    const fp4 y = fp4_sqr_k6(x), d = fp4_sqr_dot(x), k7 = fp4_sqr_k7(x);
+    const fp2 want_a = fp2_add(fp2_sqr(x.a), fp2_mul_xi(fp2_sqr(x.b)));
+    const fp2 want_b = fp2_dbl(fp2_mul(x.a, x.b));
+    bool ok = fp2_eq(y.a, want_a) && fp2_eq(y.b, want_b) && fp2_eq(y.a, d.a) && fp2_eq(y.b, d.b) && fp2_eq(y.a, k7.a) && fp2_eq(y.b, k7.b);
+    for (const fp* c : {&y.a.c0, &y.a.c1, &y.b.c0, &y.b.c1}) ok = ok && lt2p(*c);
+    bad += !ok;
+    cases++;
+    // how often the signed Y.b.c0 took its + p (a diagnostic: the branch is exercised)
+    uint32_t a0[14], a1[14], b0[14], b1[14], t0[14], t1[14], t2[14], t3[14];
+    fp_split28(fp_to_u12(x.a.c0), a0);
+    fp_split28(fp_to_u12(x.a.c1), a1);
+    fp_split28(fp_to_u12(x.b.c0), b0);
+    fp_split28(fp_to_u12(x.b.c1), b1);
+    bool n0, n1, n2;
+    fp4_sqr_k6_t(a0, a1, b0, b1, t0, t1, t2, t3, n0, n1, n2);
+    negfix += n2;
+    return n2;
+  };
+  for (unsigned long t = 0; t < n; t++) check(fp4{{rnd(), rnd()}, {rnd(), rnd()}});
+  for (int e = 0; e < 256; e++) check(fp4{{edge[e & 3], edge[(e >> 2) & 3]}, {edge[(e >> 4) & 3], edge[(e >> 6) & 3]}});
+  for (int e = 0; e < 16; e++) {  // full limbs in every subset of the components, random elsewhere, and all tops
+    auto pick = [&](int bit) { return ((e >> bit) & 1) ? full(top2p - 1) : rnd(); };
+    check(fp4{{pick(0), pick(1)}, {pick(2), pick(3)}});
+  }
+  check(fp4{{full(top2p - 1), full(top2p - 1)}, {full(top2p - 1), full(top2p - 1)}});
+  check(fp4{{full(0), full(top2p - 1)}, {full(top2p - 1), full(0)}});
+  check(fp4{{full(top2p - 1), full(0)}, {full(top2p - 1), full(0)}});
+  // Y.b.c0 = 2 (a0 b0 - a1 b1): most negative, largest; Y.b.c1 = 2 (a0 b1 + a1 b0): largest;
+  // Y.a.c0 = a0^2 - a1^2 + b0^2 - b1^2 - 2 b0 b1: most negative, largest
+  check(fp4{{edge[0], edge[3]}, {edge[0], edge[3]}});
+  check(fp4{{edge[3], edge[0]}, {edge[3], edge[0]}});
+  check(fp4{{edge[3], edge[3]}, {edge[3], edge[3]}});
+  check(fp4{{edge[0], edge[3]}, {edge[3], edge[3]}});
+  check(fp4{{edge[3], edge[0]}, {edge[3], edge[0]}});
+  // Y.b.c0 negative before its + p, by construction: a0 b0 = 0, a1 = 2^(196 + i), b1 = 2^(195 + j) give
+  // 2 (a0 b0 - a1 b1) = -R 2^(i + j), so m = 0 and the signed result is exactly -2^(i + j) (down to -2^371 at
+  // a1 = b1 = 2^381, inside (-p/315, 0)); every one must take the fix-up and come out as p - 2^(i + j)
+  unsigned long forced = 0, forced_neg = 0;
+  auto pow2 = [](int k) {
+    fp r = fp_zero();
+    r.l[k / 32] = 1u << (k % 32);
+    return r;
+  };
+  for (int i = 0; i <= 185; i += 37)
+    for (int j = 0; j <= 186; j += 62) {
+      forced_neg += check(fp4{{edge[0], pow2(196 + i)}, {edge[0], pow2(195 + j)}});
+      forced_neg += check(fp4{{rnd(), pow2(196 + i)}, {edge[0], pow2(195 + j)}});  // a0 b0 = 0 still
+      forced_neg += check(fp4{{edge[0], pow2(196 + i)}, {rnd(), pow2(195 + j)}});
+      forced += 3;
+    }
+  // near the extremes, the low words random: about one in 315 of the first kind comes out negative
+  // before its + p (m p < 8 p^2), against next to none of uniform operands
+  for (unsigned long t = 0; t < n; t++) {
+    auto near = [&](bool big) {
+      fp x = big ? edge[3] : edge[0];
+      for (int i = 0; i < 6; i++) x.l[i] = big ? x.l[i] - (next() & 0xffffu) - 1u : next();
+      return x;
+    };
+    check(fp4{{near(false), near(true)}, {near(false), near(true)}});
+    check(fp4{{near(true), near(false)}, {near(true), near(false)}});
+  }
+
+  // the three-lane Granger-Scott square (tri.h tri_cyclotomic_sqr without its lane exchange)
+  unsigned long bad_cyc = 0, cyc = 0;
+  for (unsigned long t = 0; t < n / 64 + 2; t++) {
+    fp12 f;
+    fp2* c[6] = {&f.c0.c0, &f.c0.c1, &f.c0.c2, &f.c1.c0, &f.c1.c1, &f.c1.c2};
+    for (auto* x : c) *x = fp2{rnd(), rnd()};
+    fp12 g = fexp_easy(f);  // cyclotomic
+    for (int it = 0; it < 63; it++) {  // as many squares as one x-power takes
+      const fp4 A[3] = {{g.c0.c0, g.c1.c1}, {g.c1.c0, g.c0.c2}, {g.c0.c1, g.c1.c2}};
+      const fp4 S[3] = {fp4_sqr_cyc(A[0]), fp4_sqr_cyc(A[1]), fp4_sqr_cyc(A[2])};
+      auto three = [](const fp2& u) { return fp2_add(fp2_dbl(u), u); };
+      // role 0, 2: (3 Y.a - 2 a, 3 Y.b + 2 b), Y = own square (role 0), role 1's (role 2)
+      // role 1:    (3 xi Y.b + 2 a, 3 Y.a - 2 b), Y = role 2's square
+      const fp4 R0 = {fp2_sub(three(S[0].a), fp2_dbl(A[0].a)), fp2_add(three(S[0].b), fp2_dbl(A[0].b))};
+      const fp4 R2 = {fp2_sub(three(S[1].a), fp2_dbl(A[2].a)), fp2_add(three(S[1].b), fp2_dbl(A[2].b))};
+      const fp4 R1 = {fp2_add(three(fp2_mul_xi(S[2].b)), fp2_dbl(A[1].a)), fp2_sub(three(S[2].a), fp2_dbl(A[1].b))};
+      fp12 h;
+      h.c0.c0 = R0.a, h.c1.c1 = R0.b, h.c1.c0 = R1.a, h.c0.c2 = R1.b, h.c0.c1 = R2.a, h.c1.c2 = R2.b;
+      const fp12 want = fp12_cyclotomic_sqr(g);
+      bad_cyc += !fp12_eq(h, want) || !fp12_eq(want, fp12_sqr(g));
+      cyc++;
+      g = h;
+    }
+  }
+  printf("{\"k6_selected\": %d, \"cases\": %lu, \"k6_mismatch\": %lu, \"yb_c0_negative\": %lu, \"yb_c0_forced_cases\": %lu, \"yb_c0_forced_negative\": %lu, \"cyclotomic_cases\": %lu, \"cyclotomic_mismatch\": %lu}\n",
+         (int)BLS_FP4_SQR_K6, cases, bad, negfix, forced, forced_neg, cyc, bad_cyc);
+  return (bad || bad_cyc) ? 1 : 0;
+}
+
 // ops: the raw operation hooks of drand_amd/csrc/testops.h on the host build (kind 0: the forms this
 // build contains, KpMad in place of the LDS tables of k p). Reads one item per line from stdin: the op's
 // name, then its operands, each Fp element as 96 hex digits (its twelve 32-bit words, most significant
@@ -1450,6 +1581,7 @@ int main(int argc, char** argv) {
   if (argc == 3 && !strcmp(argv[1], "addfuzz")) return cmd_addfuzz(strtoul(argv[2], nullptr, 10));
   if (argc == 3 && !strcmp(argv[1], "linfuzz")) return cmd_linfuzz(strtoul(argv[2], nullptr, 10));
   if (argc == 3 && !strcmp(argv[1], "f6fuzz")) return cmd_f6fuzz(strtoul(argv[2], nullptr, 10));
+  if (argc == 3 && !strcmp(argv[1], "sq6fuzz")) return cmd_sq6fuzz(strtoul(argv[2], nullptr, 10));
   if (argc != 5) {
     fprintf(stderr, "usage: %s pk48hex round prevhex|- sig96hex   (prev '-' = unchained V2)\n       %s hash msghex\n"
             "       %s tlock sig96hex   (one compressed U in hex per line on stdin)\n"
