@@ -128,6 +128,8 @@ SIGNATURES = {
     "blsv_tlock_lat_stats": (ctypes.c_int, [vp, u64p, u64p]),
     "blsv_set_tseal_lat_max": (sz, [vp, sz]),
     "blsv_tseal_lat_stats": (ctypes.c_int, [vp, u64p, u64p]),
+    "blsv_set_sign_lat_max": (sz, [vp, sz]),
+    "blsv_sign_lat_stats": (ctypes.c_int, [vp, u64p, u64p]),
     "blsv_set_tauth_lat_max": (sz, [vp, sz, sz]),
     "blsv_tauth_lat_stats": (ctypes.c_int, [vp, u64p, u64p, u64p, u64p]),
     "blsv_test_tauth_walk_waves": (ctypes.c_int, [vp, ctypes.c_int]),

@@ -43,6 +43,7 @@ int ensure_workspace(blsv_ctx* c, size_t cnt) {
     c->tseal_lat.lat_max = std::min(c->tseal_lat.lat_max, c->chunk);
     c->tauth_lat.open_max = std::min(c->tauth_lat.open_max, c->chunk);
     c->tauth_lat.seal_max = std::min(c->tauth_lat.seal_max, c->chunk);
+    c->sign_lat.lat_max = std::min(c->sign_lat.lat_max, c->chunk);
     c->oom_halvings++;
   }
 }
@@ -124,6 +125,7 @@ int blsv_create(int device, blsv_ctx** out) {
   c->tseal_lat.lat_max = std::min(tseal_lat_max_env(), c->chunk);
   c->tauth_lat.open_max = std::min(tauth_lat_max_env("BLSV_TAUTH_OPEN_LAT_MAX"), c->chunk);
   c->tauth_lat.seal_max = std::min(tauth_lat_max_env("BLSV_TAUTH_SEAL_LAT_MAX"), c->chunk);
+  c->sign_lat.lat_max = std::min(sign_lat_max_env(), c->chunk);
   hipError_t e = hipSetDevice(device);
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
   if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking);
@@ -266,6 +268,21 @@ int blsv_tauth_lat_stats(blsv_ctx* c, uint64_t* open_launches, uint64_t* open_it
   return BLSV_OK;
 }
 
+// cutover of the signing's latency path (include/blsverify.h "Signing on the latency path"; 0 = off)
+size_t blsv_set_sign_lat_max(blsv_ctx* c, size_t items) {
+  if (!c) return 0;
+  const size_t prev = c->sign_lat.lat_max;
+  c->sign_lat.lat_max = std::min(items, c->chunk);
+  return prev;
+}
+
+int blsv_sign_lat_stats(blsv_ctx* c, uint64_t* launches, uint64_t* items) {
+  if (!c) return BLSV_EINVAL;
+  if (launches) *launches = c->sign_lat.launches;
+  if (items) *items = c->sign_lat.items;
+  return BLSV_OK;
+}
+
 // per-context pass size (include/blsverify.h memory contract)
 size_t blsv_set_chunk(blsv_ctx* c, size_t items) {
   if (!c) return 0;
@@ -284,6 +301,7 @@ size_t blsv_set_chunk(blsv_ctx* c, size_t items) {
   c->tseal_lat.lat_max = std::min(c->tseal_lat.lat_max, v);
   c->tauth_lat.open_max = std::min(c->tauth_lat.open_max, v);
   c->tauth_lat.seal_max = std::min(c->tauth_lat.seal_max, v);
+  c->sign_lat.lat_max = std::min(c->sign_lat.lat_max, v);
   return prev;
 }
 

@@ -351,6 +351,10 @@ inline size_t tauth_lat_max_env(const char* name) {
   return (size_t)std::min<unsigned long long>(x, kMaxChunk);
 }
 
+// Cutover of the signing's latency path (blsv_set_sign_lat_max): BLSV_SIGN_LAT_MAX, parsed as
+// BLSV_TSEAL_LAT_MAX is, else 0 = off. Read once per context.
+inline size_t sign_lat_max_env() { return tauth_lat_max_env("BLSV_SIGN_LAT_MAX"); }
+
 struct rlc_state {
   size_t group = kRlcGroupDefault;
   bool seed_pinned = false;  // blsv_test_rlc_seed
@@ -445,6 +449,16 @@ struct tauth_lat_state {
   TlockLatPlan plan;
 };
 
+// Signing on the latency path (blsv_set_sign_lat_max, k_lat_sign.hip): blsv_sign calls of up to lat_max
+// messages, one workgroup per message. Its own device buffer (hostlogic.h sign_lat_layout), host staging and
+// counters; the pipeline staging, the batch signer's c->sk and every other counter stay as they are.
+struct sign_lat_state {
+  size_t lat_max = 0;                // never above the chunk
+  uint64_t launches = 0, items = 0;  // blsv_sign_lat_stats
+  DBuf buf;
+  std::vector<uint8_t> up, down;  // the key in `up` is cleared before the entry returns
+};
+
 struct blsv_ctx {
   int device = 0;
   bool prof = false;
@@ -514,6 +528,7 @@ struct blsv_ctx {
   tseal_lat_state tseal_lat;
   tauth_lat_state tauth_lat;
   tauth_state tauth;
+  sign_lat_state sign_lat;
 };
 
 #define HIPCHK(ctx, expr)                                                             \

@@ -257,6 +257,12 @@ int tauth_lat_seal_run(blsv_ctx* c, const uint8_t* pk48, const uint64_t* rounds,
                        const uint8_t* msgs, size_t mlen, size_t n, uint8_t* out_us48, uint8_t* out_vs32, uint8_t* out_ws,
                        uint8_t* ok);
 
+// ---- sign_lat.cpp: a blsv_sign call of n >= 1 messages on the latency path (hostlogic.h sign_lat_routes),
+// after the entry point's own argument checks. sk: the key reduced mod r (hostlogic.h scalar_mod_r); index, msgs,
+// msg_lens and out as blsv_sign takes them.
+int sign_lat_run(blsv_ctx* c, const uint32_t (&sk)[8], int32_t index, const uint8_t* msgs, const uint32_t* msg_lens,
+                 size_t n, uint8_t* out);
+
 // ---- tseal.cpp: the key a sealing call runs under -- pk48, or the group key (BLSV_ENOGROUP without one)
 int seal_key(blsv_ctx* c, const uint8_t* pk48, const uint8_t** key);
 

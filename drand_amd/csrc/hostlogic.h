@@ -575,5 +575,34 @@ inline bool tauth_lat_seal_layout(size_t n, bool rounds, size_t mlen, TauthLatSe
   return true;
 }
 
+// ---------------------------------------------------------------- signing on the latency path
+// blsv_set_sign_lat_max: a blsv_sign call of 1 .. lat_max messages goes to k_lat_sign, one workgroup per message.
+inline bool sign_lat_routes(size_t n, size_t lat_max) { return n >= 1 && n <= lat_max; }
+// One device buffer per call: what the host uploads in one copy -- the key (eight words, reduced mod r),
+// the n message offsets (8 bytes each: the buffer is 8-byte aligned), the n message lengths (4 bytes each), the
+// mbytes packed message bytes -- and, 64-byte aligned, what one download brings back: the n x 96 signature
+// bytes at stride 96 (a word array: the host puts a share index in front of each as it copies out).
+// [o_sk, o_off) is what the entry clears behind the kernel. 108 bytes per message plus its own bytes, plus
+// the 32 of the key and at most 63 of padding.
+constexpr size_t kSignLatKeyBytes = 32;
+constexpr size_t kSignLatBytesPerItem = 8 + 4 + 96;
+struct SignLatLayout {
+  size_t o_sk, o_off, o_len, o_msgs, in_total, o_out, out_total, total;
+};
+// false when a byte count does not fit size_t (l is then untouched)
+inline bool sign_lat_layout(size_t n, size_t mbytes, SignLatLayout& l) {
+  const size_t fixed = kSignLatKeyBytes + 63;
+  if (mbytes > SIZE_MAX - fixed || n > (SIZE_MAX - fixed - mbytes) / kSignLatBytesPerItem) return false;
+  l.o_sk = 0;
+  l.o_off = kSignLatKeyBytes;
+  l.o_len = l.o_off + 8 * n;
+  l.o_msgs = l.o_len + 4 * n;
+  l.in_total = l.o_msgs + mbytes;
+  l.o_out = (l.in_total + 63) & ~size_t(63);
+  l.out_total = 96 * n;
+  l.total = l.o_out + l.out_total;
+  return true;
+}
+
 }  // namespace blsv_detail
 #pragma GCC visibility pop

@@ -274,6 +274,11 @@ void launch_lat_verify_pre(const uint32_t* hout, const uint32_t* saff, uint8_t* 
 // signatures: out + i*out_stride (+2 index prefix when index >= 0) = compress(sk * H(msg_i))
 void launch_sign(const uint32_t* sk_words, int32_t index, const uint32_t* H, const uint8_t* h_inf, size_t cnt,
                  uint8_t* out, size_t out_stride, hipStream_t st);
+// signing on the latency path (k_lat_sign.hip): one workgroup per message, item i = compress(sk * H(msg_i)) for
+// the message msgs[off[i] .. off[i] + len[i]) and the key sk_words (eight little-endian words, reduced mod r)
+// -> out (n x 24 words: 96-byte signatures at stride 96, no index prefix), byte for byte launch_sign's
+void launch_lat_sign(const uint32_t* sk_words, const uint8_t* msgs, const uint64_t* off, const uint32_t* len, size_t n,
+                     uint32_t* out, hipStream_t st);
 // synthetic chained history (client/test/result/mock/result.go:98-132 recipe, per segment):
 // fills sigs (n x 96) for rounds first_round .. first_round+n-1 with the ChainedSrc seed rule
 void launch_gen_chained(const uint32_t* sk_words, const ChainedSrc& src, size_t n, uint8_t* sigs_out, hipStream_t st);

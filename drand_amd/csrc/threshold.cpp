@@ -486,6 +486,9 @@ int blsv_sign(blsv_ctx* c, const uint8_t* sk32, int32_t index, const uint8_t* ms
   if (!n) return BLSV_OK;
   uint32_t sk[8];
   scalar_mod_r(sk32, sk);
+  // a call of a few messages: one workgroup per message (sign_lat.cpp; blsv_set_sign_lat_max, 0 = off)
+  if (sign_lat_routes(n, std::min(c->sign_lat.lat_max, c->chunk)))
+    return sign_lat_run(c, sk, index, msgs, msg_lens, n, out);
   int rc = ensure_workspace(c, n);
   if (rc) return rc;
   rc = upload_messages(c, msgs, msg_lens, n);

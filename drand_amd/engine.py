@@ -398,6 +398,18 @@ class Engine:
         ob = bytes(out)
         return [ob[i * stride:(i + 1) * stride] for i in range(n)]
 
+    def set_sign_lat_max(self, items):
+        """blsv_set_sign_lat_max: sign calls of 1 .. items messages run on the latency path, one workgroup
+        per message (0 = off, the default; clamped to the chunk); the outputs are byte for byte the batch
+        path's. Returns the previous value."""
+        return int(self.lib.blsv_set_sign_lat_max(self._h, int(items)))
+
+    def sign_lat_stats(self):
+        """(latency-path signing calls, messages they signed) since the context was created."""
+        a, b = ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(self.lib.blsv_sign_lat_stats(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
+
     # ------------------------------------------------------------------ device-resident batches
     def verify_chained_dev(self, first_round, seg_len, d_seeds, seed0_len, d_sigs, n, d_bitmap, d_first_bad,
                            d_cls=None, stream=None, seg_phase=0):

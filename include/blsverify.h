@@ -228,6 +228,54 @@ int blsv_recover(blsv_ctx* ctx, const uint8_t* msg, size_t msg_len, const uint8_
 int blsv_sign(blsv_ctx* ctx, const uint8_t* sk32, int32_t index, const uint8_t* msgs, const uint32_t* msg_lens,
               size_t n, uint8_t* out);
 
+/*
+ * Signing on the latency path (opt-in). The calls a node makes are one or two messages: its V1 and V2
+ * partials once per round (chain/beacon/crypto.go:58), or one identity (key/keys.go:80-83). On the batch path
+ * such a call gives ONE lane the whole job -- hash-to-G2, a 255-bit double-and-add, the inversion, the
+ * compression -- with the chip idle. The latency engine has a signing item: one workgroup of eight waves per
+ * message hashes it (waves 0, 3, 4, 5, as a verification's hash branch), converts H to affine once, then four
+ * waves each run one 64-bit ladder [d_j] P_j of the key's digits in base |x| on P_j = (-psi)^j (H) = [|x|^j] H
+ * (63 doublings and a mixed addition per set bit, instead of 254 doublings), and wave 0 adds the four, converts
+ * and compresses (drand_amd/csrc/wsign.h, k_lat_sign.hip).
+ *
+ * blsv_set_sign_lat_max(ctx, L) returns the previous value. The default is 0 = off, or the environment
+ * variable BLSV_SIGN_LAT_MAX (a non-negative integer; anything else is ignored with a note on stderr). L is
+ * clamped to the context's chunk, here and whenever the chunk shrinks (blsv_set_chunk, the out-of-memory
+ * halving). A setter of its own: the other *_lat_max values do not move with it. With L = 0 blsv_sign behaves
+ * exactly as described above.
+ *
+ * With L > 0, blsv_sign sends a call of 1 .. L messages to the latency path, after its own argument
+ * validation (the same BLSV_EINVAL with no output touched). A call with n = 0 or n > L takes the batch path
+ * unchanged. Every output byte is what the batch path writes for the same arguments: BE16(index) in front of
+ * each signature at stride 98 when index >= 0 (the kernel writes 96-byte signatures; the host puts the two
+ * bytes in front as it copies out), stride 96 without, and the encoding of the point at infinity (0xc0, then
+ * 95 zero bytes) for a key == 0 (mod r).
+ *
+ * Counters: blsv_sign_lat_stats: *launches = latency-path calls, *items = messages they signed since the
+ * context's creation; either pointer may be NULL. No other counter moves on a latency-path call.
+ *
+ * Memory and secrecy: one device buffer of 108 bytes per message (8 offset + 4 length up, 96 down) plus the
+ * message's own bytes, 32 bytes of key and at most 63 of padding, beside the pipeline staging, which this
+ * path does not touch. The staged key -- device and host copies -- is cleared behind the kernel before the
+ * entry returns, also when the call fails. A partial product [d_j] P_j beside the public P_j is a 64-bit
+ * discrete logarithm, which is breakable where the whole signature is not: each wave overwrites the on-chip
+ * slots that held one before the workgroup exits, and none is ever written to device memory. There is NO
+ * constant-time claim: the ladders branch on the digits' bits, as the batch path's double-and-add branches
+ * on the key's.
+ *
+ * Measured on one MI355X (profiles/sign_lat_bench.json; the two modes alternating call by
+ * call in one run and each mode also timed twice in a row, medians, identical bytes in every round): a lone
+ * blsv_sign of a 32-byte message takes 1.75 ms against 17.5 ms on the batch path (10.0 times faster; two
+ * calls in a row of one mode differ by 0.01 ms on the latency path and 1.2 ms on the batch path), a node's
+ * round -- two messages with a share index in one call -- 1.75 ms against 17.6 ms; the lone verify of the same
+ * run takes 1.90 ms. n messages: 1.75 ms up to 2, 1.76 at 16, 1.78 at 64, 1.84 at 256 (one workgroup per compute
+ * unit), 3.59 at 512, 7.07 at 1,024, 14.05 at 2,048 and 27.97 at 4,096, against 16.4 - 18.2 ms on the batch path
+ * at every size. The batch path is first faster at n = 4,096 (at 2,048 the latency path still wins by 1.17).
+ * Recommended: blsv_set_sign_lat_max(ctx, 2048).
+ */
+size_t blsv_set_sign_lat_max(blsv_ctx* ctx, size_t items); /* returns the previous value */
+int blsv_sign_lat_stats(blsv_ctx* ctx, uint64_t* launches, uint64_t* items);
+
 /* ---------------------------------------------------------------- device-resident batches */
 
 /*

@@ -569,6 +569,33 @@ int test_hostlogic() {
     CHECK(!tseal_lat_layout(most + 1, true, big) && !tseal_lat_layout(SIZE_MAX, false, big));
     CHECK(big.total == keep.total && big.o_gt == keep.o_gt);  // untouched on overflow
   }
+  {
+    // the signing's latency path: routing and the buffer layout over the edge sizes, with its overflow guard
+    // (checked here only: nothing is added to the JSON)
+    CHECK(!sign_lat_routes(0, 4) && sign_lat_routes(1, 4) && sign_lat_routes(4, 4));
+    CHECK(!sign_lat_routes(5, 4) && !sign_lat_routes(1, 0) && !sign_lat_routes(0, 0));
+    static_assert(kSignLatBytesPerItem == 108 && kSignLatKeyBytes == 32, "the header states the bytes per message");
+    for (size_t n : {size_t(1), size_t(2), size_t(9), size_t(65), size_t(4096), size_t(262144)})
+      for (size_t mb : {size_t(0), size_t(1), size_t(31), size_t(32), size_t(301), size_t(1) << 33}) {
+        SignLatLayout l;
+        CHECK(sign_lat_layout(n, mb, l));
+        CHECK(l.o_sk == 0 && l.o_off == 32 && l.o_off % 8 == 0 && l.o_len == l.o_off + 8 * n && l.o_len % 4 == 0);
+        CHECK(l.o_msgs == l.o_len + 4 * n && l.in_total == l.o_msgs + mb);
+        CHECK(l.o_out >= l.in_total && l.o_out - l.in_total < 64 && l.o_out % 64 == 0);
+        CHECK(l.out_total == 96 * n && l.total == l.o_out + l.out_total);
+        CHECK(l.total <= kSignLatBytesPerItem * n + mb + kSignLatKeyBytes + 63);
+      }
+    SignLatLayout big, keep;
+    const size_t most = (SIZE_MAX - 95) / kSignLatBytesPerItem;
+    CHECK(sign_lat_layout(most, 0, big) && big.total >= big.o_out && big.total > most);
+    keep = big;
+    CHECK(!sign_lat_layout(most + 1, 0, big) && !sign_lat_layout(SIZE_MAX, 0, big));
+    CHECK(!sign_lat_layout(1, SIZE_MAX, big) && !sign_lat_layout(1, SIZE_MAX - 95, big));
+    CHECK(!sign_lat_layout(most, kSignLatBytesPerItem, big));  // the item bytes and the message bytes together
+    CHECK(sign_lat_layout(1, SIZE_MAX - 95 - kSignLatBytesPerItem, big) && big.total >= big.o_out);
+    big = keep;
+    CHECK(!sign_lat_layout(most + 1, 0, big) && big.total == keep.total && big.o_out == keep.o_out);  // untouched on overflow
+  }
   out += "]}}}";
   puts(out.c_str());
   return 0;

@@ -22,6 +22,8 @@
 //        wvtest taopen  < lines "sig96 u48 v32 w"                      -> the same by the eight-wave team
 //        wvtest aseal   < lines "pk48 round seed32 msg mode"           -> "ok u48 v32 w" (mode "-", or "k0": the refusal)
 //        wvtest taseal  < lines "pk48 round seed32 msg mode"           -> the same by the eight-wave team
+//        wvtest sign    < lines "sk32 msg" (hex; msg "-" = empty)      -> the 96 signature bytes (wsign.h sign_item)
+//        wvtest tsign   < lines "sk32 msg"                             -> the same by the eight-wave team
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
@@ -33,6 +35,7 @@
 #include "../drand_amd/csrc/wvteam.h"
 #include "../drand_amd/csrc/wseal.h"
 #include "../drand_amd/csrc/wauth.h"
+#include "../drand_amd/csrc/wsign.h"
 #include "../drand_amd/csrc/tseal.h"
 
 #include <thread>
@@ -877,7 +880,41 @@ static int cmd_aseal(bool team) {
   return 0;
 }
 
+// ------------------------------------------------------------------ signing (wsign.h)
+// sign / tsign: "sk32 msg" -> the 96 bytes of compress([sk mod r] H(msg)) through wsign.h sign_item (one wave:
+// the hash, then the four digit ladders in turn) or sign_team (one host thread per wave). The key is reduced
+// by tscalar.h, whose reduction is the host's scalar_mod_r (k mod r, zero kept). tsign aborts if a partial
+// product is still in its LDS slots when the workgroup exits.
+static int cmd_sign(bool team) {
+  static char a[300], b[4000];
+  while (scanf("%299s %3999s", a, b) == 2) {
+    const auto kb = unhex(a), msg = unhex(strcmp(b, "-") ? b : "");
+    if (kb.size() != 32) {
+      printf("-\n");
+      continue;
+    }
+    uint32_t sk[8], b0[8], out[24];
+    (void)bls::tseal_scalar(kb.data(), sk);
+    msg_b0(msg, b0);
+    memset(out, 0xee, sizeof out);
+    if (!team) {
+      wv_init();
+      sign_item(b0, sk, out);
+    } else {
+      for (int i = SIGN_PART * 64; i < SIGN_PART_END * 64; i++) g_host_blk[i] = 0xeeeeeeeeu;
+      run_team([&](int) { sign_team(b0, sk, out); });
+      if (!slots_zero(SIGN_PART, SIGN_PART_END)) fprintf(stderr, "a partial product left in its slots\n"), abort();
+    }
+    print_hex((const uint8_t*)out, 96);
+    printf("\n");
+    fflush(stdout);
+  }
+  return 0;
+}
+
 int main(int argc, char** argv) {
+  if (argc >= 2 && !strcmp(argv[1], "sign")) return cmd_sign(false);
+  if (argc >= 2 && !strcmp(argv[1], "tsign")) return cmd_sign(true);
   if (argc >= 2 && !strcmp(argv[1], "gtmid")) return cmd_gtmid();
   if (argc >= 2 && !strcmp(argv[1], "awalk")) return cmd_awalk(false);
   if (argc >= 2 && !strcmp(argv[1], "tawalk")) return cmd_awalk(true);
