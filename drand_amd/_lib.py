@@ -160,6 +160,13 @@ SIGNATURES = {
                                                        u8p, u8p]),
     "blsv_tlock_decrypt_auth_rounds_dev": (ctypes.c_int, [vp, u8p, u64p, sz, vp, vp, vp, sz, sz, ctypes.c_int, vp, vp, vp,
                                                            vp]),
+    "blsv_tlock_encrypt_auth_var": (ctypes.c_int, [vp, u8p, ctypes.c_uint64, u8p, u8p, u32p, sz, ctypes.c_int, u8p, u8p,
+                                                    u8p, u8p]),
+    "blsv_tlock_encrypt_auth_rounds_var": (ctypes.c_int, [vp, u8p, u64p, u8p, u8p, u32p, sz, ctypes.c_int, u8p, u8p, u8p,
+                                                           u8p]),
+    "blsv_tlock_decrypt_auth_var": (ctypes.c_int, [vp, u8p, u8p, u8p, u8p, u32p, sz, ctypes.c_int, u8p, u8p, u8p, u8p]),
+    "blsv_tlock_decrypt_auth_rounds_var": (ctypes.c_int, [vp, u8p, u64p, sz, u8p, u8p, u8p, u32p, sz, ctypes.c_int, u8p,
+                                                           u8p, u8p, u8p]),
 }
 
 _lib = None

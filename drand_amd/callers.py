@@ -558,7 +558,9 @@ def timelock_encrypt_rounds(engine, items, scalars=None, pk48=None) -> list:
 # Authenticated timelock (include/blsverify.h "authenticated timelock"): ciphertexts ``(U48, V32, W)`` that
 # report whether they opened. The sealing scalar is H3(seed, message), so the message LENGTH enters the
 # ciphertext: ragged inputs cannot be padded and cut back as above. They are grouped by length, one engine
-# call per distinct length, and the results come back in input order. An empty message or one above
+# call per distinct length, and the results come back in input order. With ``ragged=True`` the whole input
+# goes to the engine in ONE call instead (``Engine.tlock_*_auth*_var``: a length per item, blsverify.h "mixed
+# message lengths in one call"), with the same results; the grouping stays the default. An empty message or one above
 # ``TLOCK_MSG_MAX`` bytes raises ``ValueError``: there is no unfused function to fall back to.
 # This is the project's own instantiation (SHA-256, its own tags and Gt encoding): NOT kyber's or tlock's.
 
@@ -575,6 +577,14 @@ def _by_length(lengths) -> dict:
     for k, n in enumerate(lengths):
         groups.setdefault(n, []).append(k)
     return groups
+
+
+def _auth_groups(lengths, ragged: bool) -> list:
+    """The index lists of the engine calls: one per distinct length, or with ``ragged`` one for everything."""
+    lengths = list(lengths)
+    if ragged:
+        return [list(range(len(lengths)))] if lengths else []
+    return list(_by_length(lengths).values())
 
 
 def _auth_seeds(seeds, n):
@@ -598,16 +608,18 @@ def _auth_verify(engine, pairs):
             raise VerifyError(r, REJ_NAMES.get(cls, "bls: invalid signature"))
 
 
-def timelock_encrypt_auth(engine, round_: int, messages, seeds=None, pk48=None) -> list:
+def timelock_encrypt_auth(engine, round_: int, messages, seeds=None, pk48=None, ragged: bool = False) -> list:
     """A list of ``(U48, V32, W)``, message i locked to ``round_`` under pk48 (None = the group key) with
     ``seeds[i]`` -- 32 fresh bytes from ``secrets.token_bytes`` each when not given. One
-    ``Engine.tlock_encrypt_auth`` call per distinct message length."""
+    ``Engine.tlock_encrypt_auth`` call per distinct message length, or with ``ragged=True`` one
+    ``Engine.tlock_encrypt_auth_var`` call for all of them."""
     msgs = [bytes(m) for m in messages]
     _auth_lengths(len(m) for m in msgs)
     seeds = _auth_seeds(seeds, len(msgs))
     out = [None] * len(msgs)
-    for idx in _by_length(len(m) for m in msgs).values():
-        res = engine.tlock_encrypt_auth(round_, [seeds[k] for k in idx], [msgs[k] for k in idx], pk48=pk48)
+    call = engine.tlock_encrypt_auth_var if ragged else engine.tlock_encrypt_auth
+    for idx in _auth_groups((len(m) for m in msgs), ragged):
+        res = call(round_, [seeds[k] for k in idx], [msgs[k] for k in idx], pk48=pk48)
         for k, ok, u, v, w in zip(idx, res.ok, res.us, res.vs, res.ws):
             if not ok:
                 raise ValueError("message %d: the derived scalar is 0 mod r; draw another seed" % k)
@@ -615,16 +627,17 @@ def timelock_encrypt_auth(engine, round_: int, messages, seeds=None, pk48=None) 
     return out
 
 
-def timelock_encrypt_auth_rounds(engine, items, seeds=None, pk48=None) -> list:
+def timelock_encrypt_auth_rounds(engine, items, seeds=None, pk48=None, ragged: bool = False) -> list:
     """A list of ``(U48, V32, W)`` in the order of ``items`` = ``[(round, message), ...]``: one
-    ``Engine.tlock_encrypt_auth_rounds`` call per distinct message length."""
+    ``Engine.tlock_encrypt_auth_rounds`` call per distinct message length, or with ``ragged=True`` one
+    ``Engine.tlock_encrypt_auth_rounds_var`` call for all of them."""
     items = [(int(r), bytes(m)) for r, m in items]
     _auth_lengths(len(m) for _, m in items)
     seeds = _auth_seeds(seeds, len(items))
     out = [None] * len(items)
-    for idx in _by_length(len(m) for _, m in items).values():
-        res = engine.tlock_encrypt_auth_rounds([items[k][0] for k in idx], [seeds[k] for k in idx],
-                                               [items[k][1] for k in idx], pk48=pk48)
+    call = engine.tlock_encrypt_auth_rounds_var if ragged else engine.tlock_encrypt_auth_rounds
+    for idx in _auth_groups((len(m) for _, m in items), ragged):
+        res = call([items[k][0] for k in idx], [seeds[k] for k in idx], [items[k][1] for k in idx], pk48=pk48)
         for k, ok, u, v, w in zip(idx, res.ok, res.us, res.vs, res.ws):
             if not ok:
                 raise ValueError("message %d: the derived scalar is 0 mod r; draw another seed" % k)
@@ -637,12 +650,14 @@ def _auth_openable(ct) -> bool:
     return len(u) == 48 and len(v) == 32
 
 
-def timelock_decrypt_auth(engine, round_: int, sig_v2: bytes, ciphertexts, verify: bool = False) -> list:
+def timelock_decrypt_auth(engine, round_: int, sig_v2: bytes, ciphertexts, verify: bool = False,
+                          ragged: bool = False) -> list:
     """The message per ``(U48, V32, W)``, or ``None`` for every item that did not authenticate or decode (a U or
     V of the wrong length is rejected host-side). ``verify`` defaults to **False** here: the ciphertext's own
     check subsumes the beacon verification -- under a signature that is not ``round_``'s every item fails it,
     so a wrong signature yields all ``None`` and no exception. ``verify=True`` runs ``verify_unchained`` first
-    and raises ``VerifyError`` as ``timelock_decrypt`` does. One engine call per distinct W length."""
+    and raises ``VerifyError`` as ``timelock_decrypt`` does. One engine call per distinct W length, or with
+    ``ragged=True`` one ``Engine.tlock_decrypt_auth_var`` call for every item that passed the host-side check."""
     sig_v2 = bytes(sig_v2)
     cts = [(bytes(u), bytes(v), bytes(w)) for u, v, w in ciphertexts]
     _auth_lengths(len(w) for _, _, w in cts)
@@ -650,32 +665,34 @@ def timelock_decrypt_auth(engine, round_: int, sig_v2: bytes, ciphertexts, verif
         _auth_verify(engine, [(round_, sig_v2)])
     out = [None] * len(cts)
     good = [k for k, ct in enumerate(cts) if _auth_openable(ct)]
-    for idx in _by_length(len(cts[k][2]) for k in good).values():
+    call = engine.tlock_decrypt_auth_var if ragged else engine.tlock_decrypt_auth
+    for idx in _auth_groups((len(cts[k][2]) for k in good), ragged):
         idx = [good[j] for j in idx]
-        res = engine.tlock_decrypt_auth(sig_v2, [cts[k][0] for k in idx], [cts[k][1] for k in idx],
-                                        [cts[k][2] for k in idx])
+        res = call(sig_v2, [cts[k][0] for k in idx], [cts[k][1] for k in idx], [cts[k][2] for k in idx])
         for k, m in zip(idx, res.msgs):
             out[k] = m
     return out
 
 
-def timelock_decrypt_auth_rounds(engine, runs, verify: bool = False) -> list:
+def timelock_decrypt_auth_rounds(engine, runs, verify: bool = False, ragged: bool = False) -> list:
     """One list of messages per ``(round, sig_v2, [(U48, V32, W), ...])``, ``None`` for every item that did not
     authenticate or decode (also every item of a round whose signature does not decode). ``verify`` as in
-    ``timelock_decrypt_auth``. One ``Engine.tlock_decrypt_auth_rounds`` call per distinct W length."""
+    ``timelock_decrypt_auth``. One ``Engine.tlock_decrypt_auth_rounds`` call per distinct W length, or with
+    ``ragged=True`` one ``Engine.tlock_decrypt_auth_rounds_var`` call."""
     runs = [(int(r), bytes(s), [(bytes(u), bytes(v), bytes(w)) for u, v, w in cts]) for r, s, cts in runs]
     _auth_lengths(len(w) for _, _, cts in runs for _, _, w in cts)
     if verify:
         _auth_verify(engine, [(r, s) for r, s, _ in runs])
     out = [[None] * len(cts) for _, _, cts in runs]
     where = [(j, k) for j, (_, _, cts) in enumerate(runs) for k, ct in enumerate(cts) if _auth_openable(ct)]
-    for idx in _by_length(len(runs[j][2][k][2]) for j, k in where).values():
+    call = engine.tlock_decrypt_auth_rounds_var if ragged else engine.tlock_decrypt_auth_rounds
+    for idx in _auth_groups((len(runs[j][2][k][2]) for j, k in where), ragged):
         picked = [where[i] for i in idx]
         per_round = [[k for jj, k in picked if jj == j] for j in range(len(runs))]
-        res = engine.tlock_decrypt_auth_rounds([s for _, s, _ in runs],
-                                               [[runs[j][2][k][0] for k in ks] for j, ks in enumerate(per_round)],
-                                               [[runs[j][2][k][1] for k in ks] for j, ks in enumerate(per_round)],
-                                               [[runs[j][2][k][2] for k in ks] for j, ks in enumerate(per_round)])
+        res = call([s for _, s, _ in runs],
+                   [[runs[j][2][k][0] for k in ks] for j, ks in enumerate(per_round)],
+                   [[runs[j][2][k][1] for k in ks] for j, ks in enumerate(per_round)],
+                   [[runs[j][2][k][2] for k in ks] for j, ks in enumerate(per_round)])
         at = 0
         for j, ks in enumerate(per_round):
             for k in ks:

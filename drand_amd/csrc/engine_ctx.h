@@ -165,6 +165,8 @@ static_assert(2 * BLSV_TLOCK_MSG_MAX <= 4 * blsk::F_WORDS,
 //                                bytes, from where the download takes them
 //   a host form, decrypting      the pass's U, V and W bytes, its message bytes and its class bytes
 // A device form that decrypts stages nothing. HQ's captured K is cleared as in blsv_tlock_encrypt (mask_wipe).
+// A ragged host form (blsv_tlock_*_auth*_var, hostlogic.h tauth_layout_var) keeps the same parts with the two
+// message regions sized by the pass's byte count, and the pass's cnt + 1 prefix offsets behind the flags.
 // T1 is the sealing's (tseal_state::t1), built on first use by whichever call needs it first.
 static_assert(BLSV_SEED_LEN == 32 && BLSV_V_LEN == 32 && BLSV_SCALAR_LEN == 32,
               "authenticated timelock: tauth_layout's rows of seeds, V bytes and scalars");
@@ -432,6 +434,7 @@ struct tseal_lat_state {
 // (hostlogic.h tauth_layout; the plan is above). No cache and no counter: a call counts in the pass it runs.
 struct tauth_state {
   DBuf buf;
+  std::vector<uint32_t> offs;  // the ragged forms: a pass's prefix offsets on the host, alive until its upload has run
 };
 
 // Authenticated timelock on the latency path (blsv_set_tauth_lat_max, k_lat_tauth_open.hip /

@@ -180,16 +180,25 @@ hipError_t mask_wipe(blsv_ctx* c, const MaskTail& mk, size_t cnt, hipStream_t st
 // blsv_tlock_decrypt_auth*, k_tauth.hip, tauth.h) in place of the mask tail. Off (the default): the pass is
 // byte for byte what it was. On: the pass runs on device pointers (MaskTail::host is false: a host form stages
 // its bytes in the feature's own buffer, engine_ctx.h) and mk.mlen is the message length.
+// The ragged forms (blsv_tlock_*_auth*_var; offs != nullptr): the items' bytes lie back to back, item i of the
+// call at offs[i] .. offs[i + 1] of rag_in and rag_out (offs: n + 1 prefix offsets on the device). The tail takes
+// its spans from here and not from the byte pointers the pass hands it, which a pass steps by mk.mlen: such a
+// call sets mk.mlen = 1, the shortest item, so that those pointers stay inside the buffers.
 struct AuthTail {
   bool on = false;
   const uint8_t* vs = nullptr;     // decrypt: the call's n x 32 V bytes
   const uint8_t* seeds = nullptr;  // encrypt: the call's n x 32 seeds
   uint8_t* out_vs = nullptr;       // encrypt: the call's n x 32 V bytes
+  const uint32_t* offs = nullptr;    // ragged: the offsets from this part's first item on
+  const uint8_t* rag_in = nullptr;   // ragged: the call's W bytes (decrypt) or message bytes (encrypt)
+  uint8_t* rag_out = nullptr;        // ragged: the call's message bytes (decrypt) or W bytes (encrypt)
+  bool rag_words = false;            // ragged: every length of the call is a multiple of 4
   AuthTail at(size_t base) const {  // the part of the pass that starts at item base
     AuthTail a = *this;
     if (vs) a.vs += base * 32;
     if (seeds) a.seeds += base * 32;
     if (out_vs) a.out_vs += base * 32;
+    if (offs) a.offs += base;
     return a;
   }
 };
@@ -249,13 +258,15 @@ int auth_t1(blsv_ctx* c, hipStream_t st);
 // tauth_lat_routes; blsv_set_tauth_lat_max), after the entry point's own argument checks. Decrypting: the
 // arguments of tlock_lat_run with the items' V and W bytes; o.gt points to the n x mlen message bytes (zeros for
 // an item whose class is not 0), so tlock_lat_copy_out with out_len = mlen hands the items over.
+// mlens != nullptr (the ragged forms): item i has mlens[i] bytes, packed back to back in ws and in o.gt, `bytes`
+// in all (hostlogic.h tauth_var_fits), and mlen is not read.
 int tauth_lat_open_run(blsv_ctx* c, const uint8_t* sigs96, size_t m, const uint32_t* sig_of, const uint32_t* idle,
                        size_t n_idle, const uint8_t* us48, const uint8_t* vs32, const uint8_t* ws, size_t mlen, size_t n,
-                       TlockLatOut& o);
+                       TlockLatOut& o, const uint32_t* mlens = nullptr, size_t bytes = 0);
 // Encrypting under the key pk48: item i to rounds[i], or every item to `round` when rounds is null
 int tauth_lat_seal_run(blsv_ctx* c, const uint8_t* pk48, const uint64_t* rounds, uint64_t round, const uint8_t* seeds32,
                        const uint8_t* msgs, size_t mlen, size_t n, uint8_t* out_us48, uint8_t* out_vs32, uint8_t* out_ws,
-                       uint8_t* ok);
+                       uint8_t* ok, const uint32_t* mlens = nullptr, size_t bytes = 0);
 
 // ---- sign_lat.cpp: a blsv_sign call of n >= 1 messages on the latency path (hostlogic.h sign_lat_routes),
 // after the entry point's own argument checks. sk: the key reduced mod r (hostlogic.h scalar_mod_r); index, msgs,

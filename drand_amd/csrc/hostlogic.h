@@ -313,6 +313,7 @@ inline bool tauth_fits(int kdf, size_t mlen, size_t n) { return tcrypt_fits(kdf,
 // plaintexts. A device form uses the scalar row alone. Every part starts on a multiple of 8.
 struct TauthLayout {
   size_t o_seeds, o_scalars, o_in, secret, o_rounds, o_us, o_vs, o_out, o_flag, total;
+  size_t o_offs;  // the ragged forms' offset table (tauth_layout_var)
 };
 inline TauthLayout tauth_layout(size_t cnt, size_t mlen) {
   const auto up8 = [](size_t v) { return (v + 7) & ~size_t(7); };
@@ -327,6 +328,55 @@ inline TauthLayout tauth_layout(size_t cnt, size_t mlen) {
   l.o_out = l.o_vs + cnt * 32;  // W bytes (encrypt) or messages (decrypt)
   l.o_flag = up8(l.o_out + cnt * mlen);  // ok bytes (encrypt) or class bytes (decrypt)
   l.total = l.o_flag + cnt;
+  l.o_offs = l.total;  // the uniform forms stage no offsets
+  return l;
+}
+
+// blsv_tlock_*_auth*_var (a length per item, the bytes packed back to back): tauth_fits' guard with every
+// mlens[i] in 1 .. BLSV_TLOCK_MSG_MAX; *total gets the call's byte count, sum mlens (below 256 n, which
+// tauth_fits' bound on n keeps inside size_t; the sum is checked all the same). n beyond the bound is refused
+// before a length is read.
+inline bool tauth_var_fits(int kdf, const uint32_t* mlens, size_t n, size_t* total) {
+  if (!tauth_fits(kdf, BLSV_TLOCK_MSG_MAX, n) || (n && !mlens)) return false;
+  size_t sum = 0;
+  for (size_t i = 0; i < n; i++) {
+    if (mlens[i] < 1 || mlens[i] > BLSV_TLOCK_MSG_MAX || mlens[i] > SIZE_MAX - sum) return false;
+    sum += mlens[i];
+  }
+  *total = sum;
+  return true;
+}
+// The offset table of the pass [base, base + cnt) of such a call: offs[i] = the bytes of the pass's items before
+// item i, offs[cnt] = the pass's byte count (returned; cnt <= 2^20 items of at most 256 bytes: below 2^32).
+// *words: every length of the pass is a multiple of 4, so with 4-byte aligned base pointers every item starts
+// and ends on a dword.
+inline size_t tauth_var_offsets(const uint32_t* mlens, size_t base, size_t cnt, uint32_t* offs, bool* words) {
+  uint32_t at = 0, low = 0;
+  for (size_t i = 0; i < cnt; i++) {
+    offs[i] = at;
+    at += mlens[base + i];
+    low |= mlens[base + i];
+  }
+  offs[cnt] = at;
+  *words = (low & 3) == 0;
+  return at;
+}
+// ... and what such a pass keeps in the staging: tauth_layout with the two message regions sized by the pass's
+// byte count, and the cnt + 1 offsets (a word array) behind the flags
+inline TauthLayout tauth_layout_var(size_t cnt, size_t bytes) {
+  const auto up8 = [](size_t v) { return (v + 7) & ~size_t(7); };
+  TauthLayout l;
+  l.o_seeds = 0;
+  l.o_scalars = l.o_seeds + cnt * 32;
+  l.o_in = l.o_scalars + cnt * BLSV_SCALAR_LEN;
+  l.secret = up8(l.o_in + bytes);
+  l.o_rounds = l.secret;
+  l.o_us = l.o_rounds + cnt * 8;
+  l.o_vs = l.o_us + cnt * BLSV_U_LEN;
+  l.o_out = l.o_vs + cnt * 32;
+  l.o_flag = up8(l.o_out + bytes);
+  l.o_offs = up8(l.o_flag + cnt);
+  l.total = l.o_offs + 4 * (cnt + 1);
   return l;
 }
 
@@ -531,6 +581,7 @@ inline bool tauth_lat_routes(size_t n, size_t lat_max) { return n >= 1 && n <= l
 // n x mlen message bytes, the n item classes, the m signature classes.
 struct TauthLatOpenLayout {
   size_t o_sigs, o_us, o_vs, o_sigof, o_idle, o_ws, in_total, o_out, o_cls, o_sigcls, out_total, total;
+  size_t o_offs;  // the ragged forms' n + 1 offsets, in front of the W bytes (tauth_lat_open_layout_var)
 };
 // false when a byte count does not fit size_t or mlen is out of range (l is then untouched). Every signature
 // has an item or is idle, so m <= n + n_idle bounds the signatures.
@@ -544,9 +595,36 @@ inline bool tauth_lat_open_layout(size_t m, size_t n, bool rounds, size_t n_idle
   l.o_sigof = l.o_vs + 32 * n;
   l.o_idle = l.o_sigof + (rounds ? 4 * n : 0);
   l.o_ws = l.o_idle + 4 * n_idle;
+  l.o_offs = l.o_ws;  // none
   l.in_total = l.o_ws + mlen * n;
   l.o_out = (l.in_total + 63) & ~size_t(63);
   l.o_cls = l.o_out + mlen * n;
+  l.o_sigcls = l.o_cls + n;
+  l.out_total = l.o_sigcls + m - l.o_out;
+  l.total = l.o_sigcls + m;
+  return true;
+}
+// whether `bytes` can be the byte count of n items of 1 .. BLSV_TLOCK_MSG_MAX bytes each
+inline bool tauth_var_bytes_ok(size_t n, size_t bytes) {
+  return bytes >= n && bytes / BLSV_TLOCK_MSG_MAX + (bytes % BLSV_TLOCK_MSG_MAX != 0) <= n;
+}
+// The ragged forms' (blsv_tlock_decrypt_auth*_var): the same, with the n + 1 prefix offsets of the items (a word
+// array, behind idle) uploaded in front of the W bytes, and `bytes` = the call's byte count (n .. 256 n, which the
+// caller has checked: tauth_var_fits) in place of mlen * n
+inline bool tauth_lat_open_layout_var(size_t m, size_t n, bool rounds, size_t n_idle, size_t bytes, TauthLatOpenLayout& l) {
+  if (n_idle > SIZE_MAX - n || !tauth_var_bytes_ok(n, bytes)) return false;
+  const size_t q = n + n_idle;
+  if (m > q || q > (SIZE_MAX - 63 - 4) / (96 + 1 + 4 + BLSV_U_LEN + 32 + 4 + 1 + 4 + 2 * BLSV_TLOCK_MSG_MAX)) return false;
+  l.o_sigs = 0;
+  l.o_us = 96 * m;
+  l.o_vs = l.o_us + BLSV_U_LEN * n;
+  l.o_sigof = l.o_vs + 32 * n;
+  l.o_idle = l.o_sigof + (rounds ? 4 * n : 0);
+  l.o_offs = l.o_idle + 4 * n_idle;
+  l.o_ws = l.o_offs + 4 * (n + 1);
+  l.in_total = l.o_ws + bytes;
+  l.o_out = (l.in_total + 63) & ~size_t(63);
+  l.o_cls = l.o_out + bytes;
   l.o_sigcls = l.o_cls + n;
   l.out_total = l.o_sigcls + m - l.o_out;
   l.total = l.o_sigcls + m;
@@ -559,6 +637,7 @@ inline bool tauth_lat_open_layout(size_t m, size_t n, bool rounds, size_t n_idle
 // copy. No scalar, no k pk and no K is ever in this buffer.
 struct TauthLatSealLayout {
   size_t o_rounds, o_seeds, o_msgs, in_total, o_us, o_vs, o_ws, o_ok, out_total, total;
+  size_t o_offs;  // the ragged forms' n + 1 offsets, in front of the seeds (tauth_lat_seal_layout_var)
 };
 inline bool tauth_lat_seal_layout(size_t n, bool rounds, size_t mlen, TauthLatSealLayout& l) {
   if (mlen < 1 || mlen > BLSV_TLOCK_MSG_MAX || n > (SIZE_MAX - 63) / (8 + 32 + BLSV_U_LEN + 32 + 1 + 2 * mlen)) return false;
@@ -570,6 +649,27 @@ inline bool tauth_lat_seal_layout(size_t n, bool rounds, size_t mlen, TauthLatSe
   l.o_vs = l.o_us + BLSV_U_LEN * n;
   l.o_ws = l.o_vs + 32 * n;
   l.o_ok = l.o_ws + mlen * n;
+  l.out_total = l.o_ok + n - l.o_us;
+  l.total = l.o_ok + n;
+  l.o_offs = l.o_seeds;  // none
+  return true;
+}
+// The ragged forms' (blsv_tlock_encrypt_auth*_var): the same, with the n + 1 prefix offsets of the items (a word
+// array) between the rounds and the seeds -- outside [o_seeds, in_total), which holds what is secret -- and
+// `bytes` = the call's byte count (tauth_var_fits has checked it) in place of mlen * n
+inline bool tauth_lat_seal_layout_var(size_t n, bool rounds, size_t bytes, TauthLatSealLayout& l) {
+  if (!tauth_var_bytes_ok(n, bytes) ||
+      n > (SIZE_MAX - 63 - 4) / (8 + 4 + 32 + BLSV_U_LEN + 32 + 1 + 2 * BLSV_TLOCK_MSG_MAX))
+    return false;
+  l.o_rounds = 0;
+  l.o_offs = rounds ? 8 * n : 0;
+  l.o_seeds = l.o_offs + 4 * (n + 1);
+  l.o_msgs = l.o_seeds + 32 * n;
+  l.in_total = l.o_msgs + bytes;
+  l.o_us = (l.in_total + 63) & ~size_t(63);
+  l.o_vs = l.o_us + BLSV_U_LEN * n;
+  l.o_ws = l.o_vs + 32 * n;
+  l.o_ok = l.o_ws + bytes;
   l.out_total = l.o_ok + n - l.o_us;
   l.total = l.o_ok + n;
   return true;

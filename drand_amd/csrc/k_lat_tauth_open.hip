@@ -23,11 +23,14 @@ static_assert(TSEAL_WINDOWS * TSEAL_ENTRIES * 24 == (int)kTsealT1Words, "wauth.h
 // (zeros unless its class is 0) and its class to cls[i]. Items that share a signature each decode it again
 // and each write its class to sig_cls[j]: the same byte. Workgroup n_items + k classes the signature
 // idle[k], which has no item. walk_waves: the waves that share the check's walk, 8 or 1 (wauth.h).
+// offs != nullptr (blsv_tlock_decrypt_auth*_var): item i's W and message bytes lie at offs[i] .. offs[i + 1] of
+// ws and out instead, n_items + 1 prefix offsets; the length is one per workgroup either way.
 __global__ void __launch_bounds__(64 * WV_WAVES) k_lat_tauth_open(const uint8_t* sigs, const uint32_t* sig_of,
                                                                  const uint8_t* us, const uint8_t* vs, const uint8_t* ws,
                                                                  uint32_t mlen, size_t n_items, const uint32_t* idle,
                                                                  size_t n_idle, const uint32_t* T1, uint8_t* out,
-                                                                 uint8_t* cls, uint8_t* sig_cls, int walk_waves) {
+                                                                 uint8_t* cls, uint8_t* sig_cls, int walk_waves,
+                                                                 const uint32_t* offs) {
   const size_t i = blockIdx.x;
   if (i >= n_items + n_idle) return;
   wv::team_init();
@@ -36,8 +39,10 @@ __global__ void __launch_bounds__(64 * WV_WAVES) k_lat_tauth_open(const uint8_t*
   if (i < n_items) {
     const size_t j = sig_of ? sig_of[i] : 0;
     uint8_t sc = 0;
-    const uint8_t c = wv::auth_open_team(sigs + 96 * j, us + 48 * i, vs + TAUTH_V_LEN * i, ws + (size_t)mlen * i, mlen, T1,
-                                         out + (size_t)mlen * i, sc, walk_waves);
+    const size_t off = offs ? (size_t)offs[i] : (size_t)mlen * i;
+    if (offs) mlen = offs[i + 1] - offs[i];
+    const uint8_t c = wv::auth_open_team(sigs + 96 * j, us + 48 * i, vs + TAUTH_V_LEN * i, ws + off, mlen, T1, out + off, sc,
+                                         walk_waves);
     if (threadIdx.x == 0) {
       cls[i] = c;
       sig_cls[j] = sc;
@@ -52,10 +57,10 @@ __global__ void __launch_bounds__(64 * WV_WAVES) k_lat_tauth_open(const uint8_t*
 void launch_lat_tauth_open(const uint8_t* sigs, const uint32_t* sig_of, const uint8_t* us, const uint8_t* vs,
                            const uint8_t* ws, size_t mlen, size_t n_items, const uint32_t* idle, size_t n_idle,
                            const uint32_t* T1, uint8_t* out, uint8_t* cls, uint8_t* sig_cls, int walk_waves,
-                           hipStream_t st) {
+                           hipStream_t st, const uint32_t* offs) {
   if (!(n_items + n_idle)) return;
   hipLaunchKernelGGL(k_lat_tauth_open, dim3((unsigned)(n_items + n_idle)), dim3(64 * WV_WAVES), 0, st, sigs, sig_of, us, vs,
-                     ws, (uint32_t)mlen, n_items, idle, n_idle, T1, out, cls, sig_cls, walk_waves == 1 ? 1 : 8);
+                     ws, (uint32_t)mlen, n_items, idle, n_idle, T1, out, cls, sig_cls, walk_waves == 1 ? 1 : 8, offs);
 }
 
 }  // namespace blsk

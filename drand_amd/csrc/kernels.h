@@ -199,6 +199,16 @@ void launch_tauth_seal_tail(const uint32_t* E, const uint8_t* cls, size_t cnt, c
 void launch_tauth_open_tail(const uint32_t* E, const uint32_t* U, const uint8_t* u_inf, uint8_t* cls, size_t cnt,
                             const uint32_t* T1, const uint8_t* vs, const uint8_t* ws, size_t mlen, uint8_t* out,
                             hipStream_t st);
+// ... and their ragged forms (blsv_tlock_*_auth*_var): item i's bytes lie at offs[i] .. offs[i + 1] of the packed
+// message pointers, offs = cnt + 1 prefix offsets on the device, every length 1 .. 256 (the host has checked).
+// words: every length is a multiple of 4; dwords then move when the message pointers are 4-byte aligned too.
+void launch_tauth_derive_var(const uint8_t* seeds, const uint8_t* msgs, size_t cnt, const uint32_t* offs, bool words,
+                             uint8_t* scalars, hipStream_t st);
+void launch_tauth_seal_tail_var(const uint32_t* E, const uint8_t* cls, size_t cnt, const uint8_t* seeds, const uint8_t* msgs,
+                                const uint32_t* offs, bool words, uint8_t* out_vs, uint8_t* out_ws, hipStream_t st);
+void launch_tauth_open_tail_var(const uint32_t* E, const uint32_t* U, const uint8_t* u_inf, uint8_t* cls, size_t cnt,
+                                const uint32_t* T1, const uint8_t* vs, const uint8_t* ws, const uint32_t* offs, bool words,
+                                uint8_t* out, hipStream_t st);
 
 // ---- latency path (k_lat.hip): one workgroup per item, the whole verification; writes cls[i] (REJ_*)
 int lat_trace_read(uint64_t* out, int n, hipStream_t st);  // phase marks of item 0 (wteam.h WV_MARK)
@@ -239,16 +249,19 @@ void launch_pubpoly_eval(const uint32_t* commits, const uint8_t* commit_inf, uin
 // bytes, 1 .. 256, packed) beside its U; out gets n_items x mlen message bytes (zeros unless cls[i] == 0) -- byte
 // for byte what launch_tauth_open_tail gives behind the batch passes. T1: kTsealT1Words words (launch_tseal_g1_table).
 // walk_waves: the waves that share the check's walk, 8 or 1 (the same bytes either way).
+// offs (optional, the ragged forms): n_items + 1 prefix offsets on the device; item i's W and message bytes then
+// lie at offs[i] .. offs[i + 1] of ws and out, and mlen is not read.
 void launch_lat_tauth_open(const uint8_t* sigs, const uint32_t* sig_of, const uint8_t* us, const uint8_t* vs,
                            const uint8_t* ws, size_t mlen, size_t n_items, const uint32_t* idle, size_t n_idle,
                            const uint32_t* T1, uint8_t* out, uint8_t* cls, uint8_t* sig_cls, int walk_waves,
-                           hipStream_t st);
+                           hipStream_t st, const uint32_t* offs = nullptr);
 // Sealing: launch_lat_tseal's item shape with the item's seed (32 bytes) and message (mlen bytes, packed) in the
 // scalar's place; us (4-byte aligned) n x 48, vs n x 32, ws n x mlen, ok n -- byte for byte what launch_tauth_derive,
 // the sealing passes and launch_tauth_seal_tail give. Neither the derived scalar nor K is written anywhere.
+// offs (optional, the ragged forms): n + 1 prefix offsets on the device, as above, for msgs and ws.
 void launch_lat_tauth_seal(const uint32_t* T1, const uint32_t* TK, const uint64_t* rounds, uint64_t round,
                            const uint8_t* seeds, const uint8_t* msgs, size_t mlen, size_t n, uint8_t* us, uint8_t* vs,
-                           uint8_t* ws, uint8_t* ok, hipStream_t st);
+                           uint8_t* ws, uint8_t* ok, hipStream_t st, const uint32_t* offs = nullptr);
 
 // decode only on the latency engine (k_lat.hip; one two-wave workgroup per signature)
 void launch_lat_decode(const uint8_t* sigs, size_t stride, size_t offset, size_t cnt, uint32_t* S, uint8_t* s_inf,

@@ -238,6 +238,21 @@ DI void tauth_h4_xor(const uint32_t (&seed)[8], const uint8_t* in, uint32_t mlen
   }
 }
 
+// Where item i of a pass lies in the pass's packed message bytes. Uniform (blsv_tlock_*_auth*): every item has
+// mlen bytes, item i from byte i * mlen. Ragged (blsv_tlock_*_auth*_var): a table of cnt + 1 prefix offsets the
+// host staged, item i in [offs[i], offs[i + 1]), its length 1 .. TMASK_MSG_MAX (the host has checked it). The
+// kernels of k_tauth.hip take either; the per-item forms below take the pointer and the length as ever.
+struct tauth_span_uniform {
+  uint32_t mlen;
+  DI size_t off(size_t i) const { return i * mlen; }
+  DI uint32_t len(size_t) const { return mlen; }
+};
+struct tauth_span_ragged {
+  const uint32_t* offs;
+  DI size_t off(size_t i) const { return offs[i]; }
+  DI uint32_t len(size_t i) const { return offs[i + 1] - offs[i]; }
+};
+
 // k = H3(seed, msg[0 .. mlen)): what k_tauth_derive runs. seed32: the 32 bytes as they are in memory.
 DI void tauth_seed_words(uint32_t (&seed)[8], const uint8_t* seed32) {
 #pragma unroll

@@ -12,11 +12,13 @@
 // caller to copy out: blsv_tlock_decrypt_auth hands nothing over under a rejected sigma.
 int tauth_lat_open_run(blsv_ctx* c, const uint8_t* sigs96, size_t m, const uint32_t* sig_of, const uint32_t* idle,
                        size_t n_idle, const uint8_t* us48, const uint8_t* vs32, const uint8_t* ws, size_t mlen, size_t n,
-                       TlockLatOut& o) {
+                       TlockLatOut& o, const uint32_t* mlens, size_t bytes) {
   tauth_lat_state& t = c->tauth_lat;
   TauthLatOpenLayout l;
-  if (!tauth_lat_open_layout(m, n, sig_of != nullptr, n_idle, mlen, l))
+  if (!(mlens ? tauth_lat_open_layout_var(m, n, sig_of != nullptr, n_idle, bytes, l)
+              : tauth_lat_open_layout(m, n, sig_of != nullptr, n_idle, mlen, l)))
     return fail(c, BLSV_EINVAL, "tlock_decrypt_auth: too many items");
+  if (!mlens) bytes = mlen * n;
   int rc = auth_t1(c, c->stream);
   if (rc) return rc;
   HIPCHK(c, t.buf.ensure(l.total));
@@ -26,16 +28,21 @@ int tauth_lat_open_run(blsv_ctx* c, const uint8_t* sigs96, size_t m, const uint3
   memcpy(t.up.data() + l.o_vs, vs32, BLSV_V_LEN * n);
   if (sig_of) memcpy(t.up.data() + l.o_sigof, sig_of, 4 * n);
   if (n_idle) memcpy(t.up.data() + l.o_idle, idle, 4 * n_idle);
-  memcpy(t.up.data() + l.o_ws, ws, mlen * n);
+  if (mlens) {
+    bool words;
+    (void)tauth_var_offsets(mlens, 0, n, (uint32_t*)(t.up.data() + l.o_offs), &words);  // a word array: o_offs % 4 == 0
+  }
+  memcpy(t.up.data() + l.o_ws, ws, bytes);
   uint8_t* d = t.buf.as<uint8_t>();
   HIPCHK(c, h2d(c, d, t.up.data(), l.in_total));
   blsk::launch_lat_tauth_open(d + l.o_sigs, sig_of ? (const uint32_t*)(d + l.o_sigof) : nullptr, d + l.o_us, d + l.o_vs,
                               d + l.o_ws, mlen, n, (const uint32_t*)(d + l.o_idle), n_idle, c->tseal.t1.as<uint32_t>(),
-                              d + l.o_out, d + l.o_cls, d + l.o_sigcls, t.walk_waves, c->stream);
+                              d + l.o_out, d + l.o_cls, d + l.o_sigcls, t.walk_waves, c->stream,
+                              mlens ? (const uint32_t*)(d + l.o_offs) : nullptr);
   HIPCHK(c, hipGetLastError());
   t.down.resize(l.out_total);
   HIPCHK(c, download_sync(c, {{t.down.data(), d + l.o_out, l.out_total}}));
-  o.gt = t.down.data();  // the n x mlen message bytes
+  o.gt = t.down.data();  // the n x mlen message bytes (ragged: the `bytes` packed ones)
   o.cls = t.down.data() + (l.o_cls - l.o_out);
   o.sig_cls = o.cls + n;
   t.open_launches++;
@@ -49,11 +56,13 @@ int tauth_lat_open_run(blsv_ctx* c, const uint8_t* sigs96, size_t m, const uint3
 // else to clear. No constant-time claim is made (tseal.h).
 int tauth_lat_seal_run(blsv_ctx* c, const uint8_t* pk48, const uint64_t* rounds, uint64_t round, const uint8_t* seeds32,
                        const uint8_t* msgs, size_t mlen, size_t n, uint8_t* out_us48, uint8_t* out_vs32, uint8_t* out_ws,
-                       uint8_t* ok) {
+                       uint8_t* ok, const uint32_t* mlens, size_t bytes) {
   tauth_lat_state& t = c->tauth_lat;
   hipStream_t st = c->stream;
   TauthLatSealLayout l;
-  if (!tauth_lat_seal_layout(n, rounds != nullptr, mlen, l)) return fail(c, BLSV_EINVAL, "tlock_encrypt_auth: too many items");
+  if (!(mlens ? tauth_lat_seal_layout_var(n, rounds != nullptr, bytes, l) : tauth_lat_seal_layout(n, rounds != nullptr, mlen, l)))
+    return fail(c, BLSV_EINVAL, "tlock_encrypt_auth: too many items");
+  if (!mlens) bytes = mlen * n;
   int rc = sealr_prepare(c, pk48, n, st);  // T1 and TK; a rejected key ends the call here
   if (rc) return rc;
   HIPCHK(c, t.buf.ensure(l.total));
@@ -61,13 +70,18 @@ int tauth_lat_seal_run(blsv_ctx* c, const uint8_t* pk48, const uint64_t* rounds,
   t.down.resize(l.out_total);
   if (rounds) memcpy(t.up.data() + l.o_rounds, rounds, 8 * n);
   memcpy(t.up.data() + l.o_seeds, seeds32, BLSV_SEED_LEN * n);
-  memcpy(t.up.data() + l.o_msgs, msgs, mlen * n);
+  if (mlens) {
+    bool words;
+    (void)tauth_var_offsets(mlens, 0, n, (uint32_t*)(t.up.data() + l.o_offs), &words);  // a word array: o_offs % 4 == 0
+  }
+  memcpy(t.up.data() + l.o_msgs, msgs, bytes);
   uint8_t* d = t.buf.as<uint8_t>();
   hipError_t e = hipMemcpyAsync(d, t.up.data(), l.in_total, hipMemcpyHostToDevice, st);
   if (e == hipSuccess) {
     blsk::launch_lat_tauth_seal(c->tseal.t1.as<uint32_t>(), c->tsealr.tk.as<uint32_t>(),
                                 rounds ? (const uint64_t*)(d + l.o_rounds) : nullptr, round, d + l.o_seeds, d + l.o_msgs, mlen,
-                                n, d + l.o_us, d + l.o_vs, d + l.o_ws, d + l.o_ok, st);
+                                n, d + l.o_us, d + l.o_vs, d + l.o_ws, d + l.o_ok, st,
+                                mlens ? (const uint32_t*)(d + l.o_offs) : nullptr);
     e = hipGetLastError();
   }
   const hipError_t wipe = hipMemsetAsync(d + l.o_seeds, 0, l.in_total - l.o_seeds, st);
@@ -79,7 +93,7 @@ int tauth_lat_seal_run(blsv_ctx* c, const uint8_t* pk48, const uint64_t* rounds,
   if (e != hipSuccess) return fail(c, BLSV_EHIP, "tlock_encrypt_auth (latency path): %s", hipGetErrorString(e));
   memcpy(out_us48, t.down.data(), BLSV_U_LEN * n);
   memcpy(out_vs32, t.down.data() + (l.o_vs - l.o_us), BLSV_V_LEN * n);
-  memcpy(out_ws, t.down.data() + (l.o_ws - l.o_us), mlen * n);
+  memcpy(out_ws, t.down.data() + (l.o_ws - l.o_us), bytes);
   memcpy(ok, t.down.data() + (l.o_ok - l.o_us), n);
   t.seal_launches++;
   t.seal_items += n;

@@ -961,6 +961,105 @@ class Engine:
         self._check(self.lib.blsv_tlock_decrypt_auth_rounds_dev(self._h, sb, cn, m, d_us, d_vs, d_ws, int(mlen), n,
                                                                 int(kdf), d_out, d_cls, d_sig_cls, stream))
 
+    # ---- mixed message lengths in one call (include/blsverify.h "mixed message lengths in one call"): the four
+    # host forms above with a length per item. The length enters H3, so nothing here pads: the bytes travel packed
+    # back to back with their lengths beside them, and every result is cut at its own length.
+    @staticmethod
+    def _ragged(items, what):
+        items = [bytes(x) for x in items]
+        lens = [len(x) for x in items]
+        if any(v >= 1 << 32 for v in lens):
+            raise ValueError("%s: a length is a uint32" % what)
+        return b"".join(items), lens, (ctypes.c_uint32 * max(len(lens), 1))(*lens)
+
+    @staticmethod
+    def _cut(buf, lens, oks):
+        b, out, at = bytes(buf), [], 0
+        for v, good in zip(lens, oks):
+            out.append(b[at:at + v] if good else None)
+            at += v
+        return out
+
+    def _encrypt_auth_var_result(self, n, lens, us, vs, ws, ok):
+        ub, vb = bytes(us), bytes(vs)
+        oks = [bool(x) for x in list(ok)[:n]]
+        return TencryptAuthResult(oks, [ub[48 * i:48 * i + 48] if oks[i] else None for i in range(n)],
+                                  [vb[32 * i:32 * i + 32] if oks[i] else None for i in range(n)], self._cut(ws, lens, oks))
+
+    def tlock_encrypt_auth_var(self, round_, seeds, msgs, pk48=None, kdf=_lib.KDF_SHA256_CTR):
+        """blsv_tlock_encrypt_auth_var: tlock_encrypt_auth over messages of ANY lengths (1 .. 256 bytes each) in one
+        call; item i's (U, V, W) are what tlock_encrypt_auth gives for it in a call of its own length."""
+        sd = self._rows(seeds, _lib.SEED_LEN, "seeds")
+        n = len(sd)
+        mb, lens, cl = self._ragged(msgs, "messages")
+        if len(lens) != n:
+            raise ValueError("one message per seed")
+        us, vs, ws, ok = _lib.out_buf(n * 48), _lib.out_buf(n * 32), _lib.out_buf(len(mb)), _lib.out_buf(n)
+        self._check(self.lib.blsv_tlock_encrypt_auth_var(self._h, self._seal_key(pk48), int(round_), _lib.buf(b"".join(sd)),
+                                                         _lib.buf(mb), cl, n, int(kdf), us, vs, ws, ok))
+        return self._encrypt_auth_var_result(n, lens, us, vs, ws, ok)
+
+    def tlock_encrypt_auth_rounds_var(self, rounds, seeds, msgs, pk48=None, kdf=_lib.KDF_SHA256_CTR):
+        """blsv_tlock_encrypt_auth_rounds_var: tlock_encrypt_auth_rounds over messages of any lengths in one call."""
+        rounds = [int(r) for r in rounds]
+        sd = self._rows(seeds, _lib.SEED_LEN, "seeds")
+        n = len(sd)
+        if len(rounds) != n:
+            raise ValueError("%d rounds for %d seeds" % (len(rounds), n))
+        if any(not 0 <= r < 1 << 64 for r in rounds):
+            raise ValueError("a round is a uint64")
+        mb, lens, cl = self._ragged(msgs, "messages")
+        if len(lens) != n:
+            raise ValueError("one message per seed")
+        us, vs, ws, ok = _lib.out_buf(n * 48), _lib.out_buf(n * 32), _lib.out_buf(len(mb)), _lib.out_buf(n)
+        self._check(self.lib.blsv_tlock_encrypt_auth_rounds_var(self._h, self._seal_key(pk48),
+                                                                (ctypes.c_uint64 * max(n, 1))(*rounds),
+                                                                _lib.buf(b"".join(sd)), _lib.buf(mb), cl, n, int(kdf), us, vs,
+                                                                ws, ok))
+        return self._encrypt_auth_var_result(n, lens, us, vs, ws, ok)
+
+    def tlock_decrypt_auth_var(self, sig, us, vs, ws, kdf=_lib.KDF_SHA256_CTR):
+        """blsv_tlock_decrypt_auth_var: tlock_decrypt_auth over ciphertexts whose W values have ANY lengths (1 .. 256
+        bytes each) in one call; msgs[i] has len(ws[i]) bytes where the item is good, else None."""
+        sig = bytes(sig)
+        if len(sig) != 96:
+            raise ValueError("the round signature is 96 bytes")
+        us = self._rows(us, 48, "U values")
+        vs = self._rows(vs, _lib.V_LEN, "V values")
+        n = len(us)
+        wb, lens, cl = self._ragged(ws, "ciphertexts")
+        if len(lens) != n or len(vs) != n:
+            raise ValueError("one V and one W per U value")
+        out, ok, cls = _lib.out_buf(len(wb)), _lib.out_buf(n), _lib.out_buf(n)
+        sc = ctypes.c_uint8()
+        rc = self.lib.blsv_tlock_decrypt_auth_var(self._h, _lib.buf(sig), _lib.buf(b"".join(us)), _lib.buf(b"".join(vs)),
+                                                  _lib.buf(wb), cl, n, int(kdf), out, ok, cls,
+                                                  ctypes.cast(ctypes.byref(sc), u8p))
+        if rc == _lib.BLSV_EINVAL and sc.value:
+            raise SignatureRejected(rc, self.lib.blsv_last_error(self._h).decode(), sc.value)
+        self._check(rc)
+        oks = [bool(x) for x in list(ok)[:n]]
+        return TdecryptAuthResult(oks, list(cls)[:n], self._cut(out, lens, oks))
+
+    def tlock_decrypt_auth_rounds_var(self, sigs, us_per_round, vs_per_round, ws_per_round, kdf=_lib.KDF_SHA256_CTR):
+        """blsv_tlock_decrypt_auth_rounds_var: tlock_decrypt_auth_rounds with W values of any lengths, also inside
+        one round's run. Returns TdecryptAuthRoundsResult in packed order."""
+        runs = [self._rows(run, 48, "U values") for run in us_per_round]
+        vruns = [self._rows(run, _lib.V_LEN, "V values") for run in vs_per_round]
+        wruns = [list(run) for run in ws_per_round]
+        if [len(r) for r in vruns] != [len(r) for r in runs] or [len(r) for r in wruns] != [len(r) for r in runs]:
+            raise ValueError("one V and one W per U value, round by round")
+        us = [u for run in runs for u in run]
+        sb, counts, m = self._rounds_args(sigs, [len(run) for run in runs])
+        n = len(us)
+        wb, lens, cl = self._ragged([w for run in wruns for w in run], "ciphertexts")
+        out, ok, cls, sc = _lib.out_buf(len(wb)), _lib.out_buf(n), _lib.out_buf(n), _lib.out_buf(m)
+        self._check(self.lib.blsv_tlock_decrypt_auth_rounds_var(self._h, sb, counts, m, _lib.buf(b"".join(us)),
+                                                                _lib.buf(b"".join(v for run in vruns for v in run)),
+                                                                _lib.buf(wb), cl, n, int(kdf), out, ok, cls, sc))
+        oks = [bool(x) for x in list(ok)[:n]]
+        return TdecryptAuthRoundsResult(oks, list(cls)[:n], self._cut(out, lens, oks), list(sc)[:m])
+
     # ------------------------------------------------------------------ stage profiling
     STAGES = ("hash", "decompress", "miller", "final_exp", "finish", "lat", "rlc", "tlock")
 

@@ -870,6 +870,59 @@ int blsv_tlock_decrypt_auth_rounds_dev(blsv_ctx* ctx, const uint8_t* sigs96, con
                                        uint8_t* d_sig_class /*optional*/, void* stream);
 
 /*
+ * Authenticated timelock, mixed message lengths in one call: blsv_tlock_encrypt_auth_var, _encrypt_auth_rounds_var,
+ * _decrypt_auth_var and _decrypt_auth_rounds_var take the argument lists of the four host forms above with
+ * `size_t mlen` replaced by `const uint32_t* mlens` (n entries; blsv_verify_messages' msg_lens is the precedent).
+ * The length enters k = H3(s, M), so a padded message is another ciphertext: these calls cannot be had by padding
+ * and cutting back, as the unauthenticated forms' can, only by one call per distinct length -- or by these.
+ *
+ * msgs, ws, out_ws and out_msgs are packed back to back in item order: item i occupies [off_i, off_i + mlens[i])
+ * with off_i = mlens[0] + ... + mlens[i - 1]. No alignment is asked for. Every mlens[i] must lie in
+ * 1 .. BLSV_TLOCK_MSG_MAX: one bad length anywhere, a kdf other than BLSV_KDF_SHA256_CTR, or a byte count that
+ * does not fit size_t returns BLSV_EINVAL with nothing touched. n == 0 reads no length.
+ *
+ * Byte identity: item i's U, V, W (or message), ok byte and class are exactly what the uniform entry point
+ * produces for that item in a call of length mlens[i]. Everything else is the uniform counterpart's: the class
+ * precedence, BLSV_REJ_TLOCK_AUTH with mlens[i] zero bytes for a failing item (its candidate plaintext never
+ * stored), the one-sigma form's BLSV_EINVAL with *sig_class set, chunked passes (a pass slices the bytes at its
+ * first item's offset), the caches and the counters, in place (out_msgs == ws, out_ws == msgs), and the
+ * clearing of staged seeds, scalars, plaintexts and K behind the kernels, also on failure. They route by
+ * blsv_set_tauth_lat_max (below) exactly as their counterparts do and move the same counters.
+ *
+ * On the device a pass stages the cnt + 1 prefix offsets of its items beside its bytes (4 bytes per item more);
+ * a lane of k_tauth.hip's ragged kernels, or a workgroup of the latency kernels, takes its span from that table.
+ * Dwords move only when every length of the pass is a multiple of 4, bytes otherwise. The lanes of a wave run
+ * 1 .. 8 pieces of 32 bytes each; nothing is sorted by length.
+ *
+ * There are no _dev forms: lengths that live on the device cannot be validated without a read-back or a reject
+ * class of their own. No ragged form of the unauthenticated blsv_tlock_encrypt* / blsv_tlock_decrypt* either:
+ * padding works there.
+ *
+ * Measured on one MI355X (profiles/tauth_var_bench.json; 65,536 items, lengths uniform in
+ * 1 .. 256, host forms, the two sides alternating call by call, medians of five pairs, identical bytes on both
+ * sides): one blsv_tlock_decrypt_auth_var call takes 24.3 ms against 3,586 ms for the 256 per-length
+ * blsv_tlock_decrypt_auth calls (148 times faster; 23.1 against 702 ms, 30 times, with those on the latency path at
+ * the recommended (1024, 512)), one blsv_tlock_encrypt_auth_var call 7.0 against 1,465 ms (209 times; 6.7 against
+ * 764 ms, 114 times). What raggedness costs: the mixed call against a uniform call of the same bytes 22.43 against
+ * 22.48 ms decrypting and 6.21 against 6.14 ms encrypting (inside the box-to-box spread); the _var entry against
+ * the uniform entry at a uniform 32 bytes 22.37 against 22.08 ms (+1.3%) and 6.50 against 6.19 ms (+5.1%: the
+ * offset table's ~0.3 ms on a 6 ms call).
+ */
+int blsv_tlock_encrypt_auth_var(blsv_ctx* ctx, const uint8_t* pk48, uint64_t round, const uint8_t* seeds32,
+                                const uint8_t* msgs, const uint32_t* mlens, size_t n, int kdf, uint8_t* out_us48,
+                                uint8_t* out_vs32, uint8_t* out_ws, uint8_t* ok);
+int blsv_tlock_encrypt_auth_rounds_var(blsv_ctx* ctx, const uint8_t* pk48, const uint64_t* rounds, const uint8_t* seeds32,
+                                       const uint8_t* msgs, const uint32_t* mlens, size_t n, int kdf, uint8_t* out_us48,
+                                       uint8_t* out_vs32, uint8_t* out_ws, uint8_t* ok);
+int blsv_tlock_decrypt_auth_var(blsv_ctx* ctx, const uint8_t* sig96, const uint8_t* us48, const uint8_t* vs32,
+                                const uint8_t* ws, const uint32_t* mlens, size_t n, int kdf, uint8_t* out_msgs, uint8_t* ok,
+                                uint8_t* reject_class /*optional*/, uint8_t* sig_class /*optional*/);
+int blsv_tlock_decrypt_auth_rounds_var(blsv_ctx* ctx, const uint8_t* sigs96, const uint64_t* counts, size_t m,
+                                       const uint8_t* us48, const uint8_t* vs32, const uint8_t* ws, const uint32_t* mlens,
+                                       size_t n, int kdf, uint8_t* out_msgs, uint8_t* ok,
+                                       uint8_t* reject_class /*optional, n*/, uint8_t* sig_class /*optional, m*/);
+
+/*
  * Authenticated timelock on the latency path: for the caller with ONE ciphertext to open or ONE message to
  * lock, or a handful. With blsv_set_tauth_lat_max(ctx, open_items, seal_items) the HOST forms
  * blsv_tlock_decrypt_auth and blsv_tlock_decrypt_auth_rounds run calls of 1 .. open_items ciphertexts, and

@@ -885,11 +885,16 @@ static int cmd_tmask() {
 // output. "forms_match": the byte stores, the dword stores (mlen a multiple of 4) and the in-place run all
 // give the same bytes, classes and scalars, and every guard is intact. "fp_mul_open": the Fp products of the
 // last good item's check (the T1 walk and the comparison).
-static int cmd_tauth() {
+// tauthv: the same with a length per case (the first line is 0): every seal case has its own message length and
+// every open case its own W length, 1 .. 256, and the packed batches take their spans from a table of prefix
+// offsets through tauth_span_ragged, as the kernels' ragged forms do. The dword form runs when every length of
+// the batch is a multiple of 4; "dword_forms": how many of the two batches ran it.
+static int cmd_tauth(bool ragged) {
   static char buf[8192];
   if (!fgets(buf, sizeof buf, stdin)) return 2;
   const unsigned long mlen = strtoul(buf, nullptr, 10);
-  if (mlen < 1 || mlen > (unsigned long)TMASK_MSG_MAX) return 2;
+  if (ragged ? mlen != 0 : (mlen < 1 || mlen > (unsigned long)TMASK_MSG_MAX)) return 2;
+  auto len_ok = [&](size_t v) { return ragged ? v >= 1 && v <= (size_t)TMASK_MSG_MAX : v == mlen; };
   struct SealIn {
     std::vector<uint8_t> seed, msg, gt;
   };
@@ -912,11 +917,11 @@ static int cmd_tauth() {
     } else if (!strcmp(cmd, "seal") && a.size() == 3) {
       seals.push_back({unhex(a[0]), unhex(a[1]), unhex(a[2])});
       const SealIn& x = seals.back();
-      if (x.seed.size() != 32 || x.msg.size() != mlen || x.gt.size() != (size_t)TMASK_GT_LEN) return 2;
+      if (x.seed.size() != 32 || !len_ok(x.msg.size()) || x.gt.size() != (size_t)TMASK_GT_LEN) return 2;
     } else if (!strcmp(cmd, "open") && (a.size() == 4 || a.size() == 5)) {
       opens.push_back({unhex(a[0]), unhex(a[1]), unhex(a[2]), unhex(a[3]), a.size() == 5 ? atoi(a[4]) : 0});
       const OpenIn& x = opens.back();
-      if (x.gt.size() != (size_t)TMASK_GT_LEN || x.u.size() != 48 || x.v.size() != 32 || x.w.size() != mlen) return 2;
+      if (x.gt.size() != (size_t)TMASK_GT_LEN || x.u.size() != 48 || x.v.size() != 32 || !len_ok(x.w.size())) return 2;
     } else {
       return 2;
     }
@@ -938,6 +943,18 @@ static int cmd_tauth() {
     tmask_midstate(mid, [&](int k) { return tmask_coef_soa(E.data(), 1, 0, k); });
   };
   bool match = true;
+  // the spans of a packed batch: the prefix offsets of its items, read through the form under test
+  auto offsets = [](size_t n, auto len_of) {
+    std::vector<uint32_t> o(n + 1, 0);
+    for (size_t i = 0; i < n; i++) o[i + 1] = o[i] + (uint32_t)len_of(i);
+    return o;
+  };
+  auto all_dwords = [](const std::vector<uint32_t>& o) {
+    uint32_t low = 0;
+    for (uint32_t v : o) low |= v;
+    return (low & 3) == 0;
+  };
+  int dword_forms = 0;
 
   printf("{\"mlen\": %lu, \"reduce\": [", mlen);
   for (size_t i = 0; i < reds.size(); i++) {
@@ -956,20 +973,24 @@ static int cmd_tauth() {
     bool operator==(const SealOut& o) const { return k == o.k && v == o.v && w == o.w && ok == o.ok; }
   };
   const size_t ns = seals.size();
+  const std::vector<uint32_t> soffs = offsets(ns, [&](size_t i) { return seals[i].msg.size(); });
+  const size_t sbytes = soffs[ns];
+  auto s_off = [&](size_t i) { return ragged ? tauth_span_ragged{soffs.data()}.off(i) : tauth_span_uniform{(uint32_t)mlen}.off(i); };
+  auto s_len = [&](size_t i) { return ragged ? tauth_span_ragged{soffs.data()}.len(i) : tauth_span_uniform{(uint32_t)mlen}.len(i); };
   auto run_seal = [&](bool words, bool in_place) {
     SealOut o;
     std::vector<uint32_t> bv, bw, bm;
     uint8_t* V = guarded(bv, 32 * ns);
-    uint8_t* W = guarded(bw, mlen * ns);
-    bm.assign(mlen * ns / 4 + 2, 0);
+    uint8_t* W = guarded(bw, sbytes);
+    bm.assign(sbytes / 4 + 2, 0);
     uint8_t* M = in_place ? W : (uint8_t*)bm.data();
-    for (size_t i = 0; i < ns; i++) memcpy(M + i * mlen, seals[i].msg.data(), mlen);
+    for (size_t i = 0; i < ns; i++) memcpy(M + s_off(i), seals[i].msg.data(), s_len(i));
     o.k.resize(32 * ns);
     for (size_t i = 0; i < ns; i++) {
       uint32_t seed[8], k[8], mid[8] = {0};
       tauth_seed_words(seed, seals[i].seed.data());
-      bool sealed = words ? tauth_derive<true>(seed, M + i * mlen, (uint32_t)mlen, k)
-                          : tauth_derive<false>(seed, M + i * mlen, (uint32_t)mlen, k);
+      bool sealed = words ? tauth_derive<true>(seed, M + s_off(i), s_len(i), k)
+                          : tauth_derive<false>(seed, M + s_off(i), s_len(i), k);
       tauth_scalar_bytes(o.k.data() + 32 * i, k);
       uint32_t k2[8];
       sealed = tseal_scalar(o.k.data() + 32 * i, k2);  // what k_tseal_u reads back from the staging row
@@ -977,23 +998,26 @@ static int cmd_tauth() {
       o.ok.push_back(sealed);
       if (sealed) gt_mid(seals[i].gt, mid);
       if (words)
-        tauth_seal_tail<true>(mid, sealed, seed, M + i * mlen, (uint32_t)mlen, V + 32 * i, W + i * mlen);
+        tauth_seal_tail<true>(mid, sealed, seed, M + s_off(i), s_len(i), V + 32 * i, W + s_off(i));
       else
-        tauth_seal_tail<false>(mid, sealed, seed, M + i * mlen, (uint32_t)mlen, V + 32 * i, W + i * mlen);
+        tauth_seal_tail<false>(mid, sealed, seed, M + s_off(i), s_len(i), V + 32 * i, W + s_off(i));
     }
-    if (!guards_ok(V, 32 * ns) || !guards_ok(W, mlen * ns)) match = false;
+    if (!guards_ok(V, 32 * ns) || !guards_ok(W, sbytes)) match = false;
     o.v.assign(V, V + 32 * ns);
-    o.w.assign(W, W + mlen * ns);
+    o.w.assign(W, W + sbytes);
     return o;
   };
   printf("], \"seal\": [");
   if (ns) {
     const SealOut o = run_seal(false, false);
     match &= run_seal(false, true) == o;
-    if (mlen % 4 == 0) match &= run_seal(true, false) == o && run_seal(true, true) == o;
+    if (all_dwords(soffs)) {
+      match &= run_seal(true, false) == o && run_seal(true, true) == o;
+      dword_forms++;
+    }
     for (size_t i = 0; i < ns; i++)
       printf("%s{\"k\": \"%s\", \"ok\": %d, \"v\": \"%s\", \"w\": \"%s\"}", i ? ", " : "", hex_of(o.k.data() + 32 * i, 32).c_str(),
-             o.ok[i], hex_of(o.v.data() + 32 * i, 32).c_str(), hex_of(o.w.data() + mlen * i, mlen).c_str());
+             o.ok[i], hex_of(o.v.data() + 32 * i, 32).c_str(), hex_of(o.w.data() + s_off(i), s_len(i)).c_str());
   }
 
   // ---- the opening side
@@ -1006,16 +1030,20 @@ static int cmd_tauth() {
     std::vector<uint8_t> msg, cls;
     bool operator==(const OpenOut& o) const { return msg == o.msg && cls == o.cls; }
   };
+  const std::vector<uint32_t> ooffs = offsets(no, [&](size_t i) { return opens[i].w.size(); });
+  const size_t obytes = ooffs[no];
+  auto o_off = [&](size_t i) { return ragged ? tauth_span_ragged{ooffs.data()}.off(i) : tauth_span_uniform{(uint32_t)mlen}.off(i); };
+  auto o_len = [&](size_t i) { return ragged ? tauth_span_ragged{ooffs.data()}.len(i) : tauth_span_uniform{(uint32_t)mlen}.len(i); };
   auto run_open = [&](bool words, bool in_place) {
     OpenOut o;
     std::vector<uint32_t> bo, bw, bv;
-    uint8_t* out = guarded(bo, mlen * no);
-    bw.assign(mlen * no / 4 + 2, 0);
+    uint8_t* out = guarded(bo, obytes);
+    bw.assign(obytes / 4 + 2, 0);
     bv.assign(8 * no + 2, 0);
     uint8_t* W = in_place ? out : (uint8_t*)bw.data();
     uint8_t* V = (uint8_t*)bv.data();
     for (size_t i = 0; i < no; i++) {
-      memcpy(W + i * mlen, opens[i].w.data(), mlen);
+      memcpy(W + o_off(i), opens[i].w.data(), o_len(i));
       memcpy(V + 32 * i, opens[i].v.data(), 32);
     }
     for (size_t i = 0; i < no; i++) {
@@ -1025,11 +1053,11 @@ static int cmd_tauth() {
       if (cls == REJ_OK && opens[i].cls) cls = (uint8_t)opens[i].cls;
       if (cls != REJ_OK) {
         const uint32_t zero[8] = {0};
-        for (uint32_t j = 0; 32 * j < mlen; j++) {
+        for (uint32_t j = 0; 32 * j < o_len(i); j++) {
           if (words)
-            tauth_store_piece<true>(out + i * mlen, j, tauth_piece_len((uint32_t)mlen, j), zero, true);
+            tauth_store_piece<true>(out + o_off(i), j, tauth_piece_len(o_len(i), j), zero, true);
           else
-            tauth_store_piece<false>(out + i * mlen, j, tauth_piece_len((uint32_t)mlen, j), zero, true);
+            tauth_store_piece<false>(out + o_off(i), j, tauth_piece_len(o_len(i), j), zero, true);
         }
       } else {
         uint32_t mid[8];
@@ -1037,25 +1065,31 @@ static int cmd_tauth() {
         const unsigned long long c0 = g_fp_mul_count;
         auto entry = [&](int w, int j) { return T1[tseal_entry(w, j)]; };
         auto ucoord = [&](int c) { return c ? U.y : U.x; };
-        cls = words ? tauth_open_tail<true>(mid, V + 32 * i, W + i * mlen, (uint32_t)mlen, ucoord, uinf, entry, out + i * mlen)
-                    : tauth_open_tail<false>(mid, V + 32 * i, W + i * mlen, (uint32_t)mlen, ucoord, uinf, entry, out + i * mlen);
+        cls = words ? tauth_open_tail<true>(mid, V + 32 * i, W + o_off(i), o_len(i), ucoord, uinf, entry, out + o_off(i))
+                    : tauth_open_tail<false>(mid, V + 32 * i, W + o_off(i), o_len(i), ucoord, uinf, entry, out + o_off(i));
         if (cls == REJ_OK) n_check = g_fp_mul_count - c0;
       }
       o.cls.push_back(cls);
     }
-    if (!guards_ok(out, mlen * no)) match = false;
-    o.msg.assign(out, out + mlen * no);
+    if (!guards_ok(out, obytes)) match = false;
+    o.msg.assign(out, out + obytes);
     return o;
   };
   printf("], \"open\": [");
   if (no) {
     const OpenOut o = run_open(false, false);
     match &= run_open(false, true) == o;
-    if (mlen % 4 == 0) match &= run_open(true, false) == o && run_open(true, true) == o;
+    if (all_dwords(ooffs)) {
+      match &= run_open(true, false) == o && run_open(true, true) == o;
+      dword_forms++;
+    }
     for (size_t i = 0; i < no; i++)
-      printf("%s{\"cls\": %d, \"msg\": \"%s\"}", i ? ", " : "", (int)o.cls[i], hex_of(o.msg.data() + mlen * i, mlen).c_str());
+      printf("%s{\"cls\": %d, \"msg\": \"%s\"}", i ? ", " : "", (int)o.cls[i], hex_of(o.msg.data() + o_off(i), o_len(i)).c_str());
   }
-  printf("], \"fp_mul_open\": %llu, \"forms_match\": %s}\n", n_check, match ? "true" : "false");
+  if (ragged)
+    printf("], \"fp_mul_open\": %llu, \"dword_forms\": %d, \"forms_match\": %s}\n", n_check, dword_forms, match ? "true" : "false");
+  else
+    printf("], \"fp_mul_open\": %llu, \"forms_match\": %s}\n", n_check, match ? "true" : "false");
   return match ? 0 : 1;
 }
 
@@ -1569,7 +1603,8 @@ int main(int argc, char** argv) {
   if (argc == 2 && !strcmp(argv[1], "subgroup")) return cmd_subgroup();
   if (argc == 3 && !strcmp(argv[1], "tlock")) return cmd_tlock(argv[2]);
   if (argc == 2 && !strcmp(argv[1], "tmask")) return cmd_tmask();
-  if (argc == 2 && !strcmp(argv[1], "tauth")) return cmd_tauth();
+  if (argc == 2 && !strcmp(argv[1], "tauth")) return cmd_tauth(false);
+  if (argc == 2 && !strcmp(argv[1], "tauthv")) return cmd_tauth(true);
   if (argc == 4 && !strcmp(argv[1], "tseal")) return cmd_tseal(argv[2], strtoull(argv[3], nullptr, 10));
   if (argc == 3 && !strcmp(argv[1], "tsealr")) return cmd_tsealr(argv[2]);
   if (argc >= 4 && !strcmp(argv[1], "tlockr")) return cmd_tlockr(argc - 2, argv + 2);
